@@ -10,7 +10,18 @@ batch of 256 images 3x224x224 per GPU.  Inputs are resident in HBM when the time
 (a pool of pre-staged device batches is cycled; the reference's per-step H2D copy is excluded).
 Weak scaling: per-GPU batch fixed, value = images of all ranks / max-over-ranks time.
 
-Rank 0 prints ONE compact JSON line (the contract object, < 4 KB, the LAST line of stdout).  The per-kernel and
+Rank 0 prints ONE compact JSON line (the contract object, < 4 KB, the LAST line of stdout).  A plain run sets up, warms
+up, times the K steps, writes `--dump-outputs DIR` if asked and prints that line (`metric`, `value`, `unit`, `ms_per_step`,
+`dtype`, `config`, ...).  Everything else it can measure or check runs only with `--full`: the objects listed below, the
+host time of one step (`step_issue.host_ms_per_step`), and for N > 1 the weights-in-sync check and the RCCL summary.
+
+--dump-outputs DIR: what the timed path computed, as DIR/<name>.npy (rank 0; about 17 MB), copied right after the last
+timed step: `logits` (fp32 [B, classes]) and `loss` of that step, `meters` (float64 [loss, prec1, prec5] as Trainer.train
+returned them), `state_sample` (fp32, a fixed seeded sample of 4 Mi entries of the model's state_dict after the step, every
+floating tensor flattened in its reference shape, in state_dict order).  Inputs and initial weights are seeded: the same
+arguments give the same inputs in every run.
+
+With --full, the per-kernel and
 per-layer tables (`kernels`, `kernels_overlapped`, `conv_layers`) go to a detail file (`--detail-out`, default
 gpurun_out/bench_detail.json; `--detail-stdout` prints them as an EARLIER {"detail": ...} line).  Objects:
   roofline     : live HIP-event timing (a separate profiled pass after the timed region) of the
@@ -114,6 +125,25 @@ def run_pmc_passes(args):
     return res
 
 
+STATE_SAMPLE = 1 << 22      # entries of the state_dict sample --dump-outputs writes (16 MB of fp32)
+
+
+def dump_outputs(out_dir, model, step_out, meters):
+    """--dump-outputs: the last timed step's (logits, loss), Trainer.train's meters and a fixed seeded sample of the
+    model's state after the step, as float32 / float64 .npy files (module docstring)."""
+    import numpy as np
+    logits, loss, _ = step_out
+    flat = torch.cat([v.detach().float().reshape(-1) for v in model.state_dict().values() if v.is_floating_point()])
+    idx = torch.randint(0, flat.numel(), (min(STATE_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(2024))
+    arrays = {'logits': logits.detach().float().cpu().numpy(),
+              'loss': loss.detach().float().reshape(1).cpu().numpy(),
+              'meters': np.array([meters['loss'], meters['prec1'], meters['prec5']], dtype=np.float64),
+              'state_sample': flat[idx.to(flat.device)].cpu().numpy()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -140,7 +170,17 @@ def main():
                     help='file for the per-kernel / per-layer tables (never part of the contract line)')
     ap.add_argument('--detail-stdout', action='store_true', help='also print the tables as an earlier {"detail": ...} line')
     ap.add_argument('--cpu-steps', type=int, default=15, help='timed steps of the CPU baseline (batch 32, 1 warm-up; ~1.7 s each)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the host time of one step, the profiled passes '
+                         '(roofline, detail tables), the CPU baseline, the measured whole-step HBM figure, and for N > 1 '
+                         'the weights-in-sync check and the RCCL summary (the --no-* options above switch parts off)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.pmc and not args.full:
+        ap.error('--pmc measures roofline.traffic, which only --full reports')
 
     if not torch.cuda.is_available():
         raise SystemExit('bench.py needs an MI355X: there is no CPU fallback for the measured path')
@@ -173,7 +213,7 @@ def main():
     torch.cuda.set_device(local_rank)
     device = torch.device('cuda', local_rank)
     rccl_log = None
-    if distributed and 'NCCL_DEBUG' not in os.environ and os.environ.get('BENCH_DIST_BACKEND', 'nccl') == 'nccl':
+    if args.full and distributed and 'NCCL_DEBUG' not in os.environ and os.environ.get('BENCH_DIST_BACKEND', 'nccl') == 'nccl':
         # what RCCL builds for this job (channels, rings / trees, transports) goes into the line: INFO-level INIT / GRAPH
         # messages into a per-process file (never stdout), read back after the communicators are up
         rccl_log = '/tmp/cn_bench_rccl_%d.log' % os.getpid()
@@ -235,25 +275,38 @@ def main():
     t_gpu0 = time.perf_counter()
     tr.train(loader(args.warmup))          # W untimed warm-up steps
     fence()
+    last = {}
+    if args.dump_outputs:
+        trainer_step = tr._step
+
+        def keep_last_step(*a, **kw):      # what a caller of the step receives: (logits, loss, grad-norm)
+            last['out'] = trainer_step(*a, **kw)
+            return last['out']
+        tr._step = keep_last_step
     t0 = time.perf_counter()
     res = tr.train(loader(args.steps))     # EXACTLY K timed steps
     torch.cuda.synchronize()
     fence()
     elapsed = time.perf_counter() - t0
-    # how the steps of the timed region were issued, and the host time one step costs (outside the timed region)
+    if args.dump_outputs:
+        tr._step = trainer_step
+        if rank == 0:      # before anything else runs a step (a launch plan's outputs are buffers the next replay rewrites)
+            dump_outputs(args.dump_outputs, tr.model, last['out'], res)
+    # how the steps of the timed region were issued, and (--full) the host time one step costs (outside the timed region)
     modes = [('plan' if g['graph'].get('plan') is not None else 'hip-graph') for g in tr._gstates.values()
              if g.get('graph') is not None]
-    with torch.cuda.stream(tr._main_stream) if tr._main_stream is not None else torch.cuda.stream(torch.cuda.current_stream(device)):
-        tr.model.train()
-        xb, tb = (t.to(device) for t in pool[0])
-        host_ms = None
-        for _ in range(0 if args.no_issue_probe else 3):          # ONE step issued into drained queues, three times (a deep backlog would make the host wait
-            fence()                 # for queue space - that is device time, not issue time), the fastest counts
-            th0 = time.perf_counter()
-            tr._step(xb, tb, training=True)
-            dt_ms = (time.perf_counter() - th0) * 1e3
-            host_ms = dt_ms if host_ms is None else min(host_ms, dt_ms)
-    fence()
+    host_ms = None
+    if args.full and not args.no_issue_probe:
+        with torch.cuda.stream(tr._main_stream) if tr._main_stream is not None else torch.cuda.stream(torch.cuda.current_stream(device)):
+            tr.model.train()
+            xb, tb = (t.to(device) for t in pool[0])
+            for _ in range(3):          # ONE step issued into drained queues, three times (a deep backlog would make the host wait
+                fence()                 # for queue space - that is device time, not issue time), the fastest counts
+                th0 = time.perf_counter()
+                tr._step(xb, tb, training=True)
+                dt_ms = (time.perf_counter() - th0) * 1e3
+                host_ms = dt_ms if host_ms is None else min(host_ms, dt_ms)
+        fence()
     step_issue = {'mode': modes[0] if modes else 'eager', 'host_ms_per_step': round(host_ms, 2) if host_ms is not None else None}
     rank_devices, params_in_sync = [local_rank], None
     if distributed:
@@ -263,9 +316,10 @@ def main():
         # which HIP device every rank ran on, by rank (one process per GPU: rank r -> device r on a full node)
         rank_devices = [None] * world
         dist.all_gather_object(rank_devices, torch.cuda.current_device())
-        # data-parallel sanity of THIS run, outside the timed region: after W + K steps on different shards every rank must
-        # hold the same master weights (same initial broadcast, same all-reduced gradients, same update) - a transport that
-        # loses or reorders a bucket shows up here, not only in a loss curve
+    if distributed and args.full:
+        # data-parallel sanity of THIS run, outside the timed region: after the steps so far on different shards every rank
+        # must hold the same master weights (same initial broadcast, same all-reduced gradients, same update) - a transport
+        # that loses or reorders a bucket shows up here, not only in a loss curve
         p32 = tr.arena.params.double()
         sig = [None] * world
         dist.all_gather_object(sig, (float(p32.sum()), float(p32.abs().sum())))
@@ -280,7 +334,7 @@ def main():
     kernels, layers, roof, kernels_ovl = {}, {}, None, {}
     nprof = 2
     agg = agg_ovl = None
-    if not args.no_kernel_profile:
+    if args.full and not args.no_kernel_profile:
         # every rank runs the profiled steps (they contain the gradient all-reduce: a rank-0-only pass would
         # wait for collectives the other ranks never enter); only rank 0 reports
         P = ca.ops.PROFILER
@@ -293,7 +347,7 @@ def main():
         tr.train(loader(nprof))
         P.enabled = False
         fence()
-    if rank == 0 and not args.no_kernel_profile:
+    if rank == 0 and args.full and not args.no_kernel_profile:
         agg = ca.ops.PROFILER.summary()
 
         def table(ag):
@@ -403,7 +457,7 @@ def main():
                     'static: profiles/%s' % pm_file
     gpu_active = time.perf_counter() - t_gpu0      # warm-up + timed region + issue probe + profiled passes (GPU busy throughout)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import convnet_oracle as O
         r = O.time_cpu_baseline(depth=args.depth, batch=32, steps=args.cpu_steps, warmup=1, size=224)
         cpu = {'value': round(r['img_per_s'], 2), 'unit': 'images/sec', 'cores': r['cores'], 'kind': 'port',
@@ -460,25 +514,26 @@ def main():
         }
         # measured HBM traffic of the whole step (all kernels, latest committed PMC passes: static, like
         # roofline.traffic) over this run's step time: how close the step as a whole runs to the memory system
-        try:
-            cands = sorted((f for f in os.listdir(os.path.join(ROOT, 'profiles')) if f.endswith('pmc_traffic.json')),
-                               key=_pmc_file_order)
-            if LIVE_PMC.get('pm') is not None:
-                pm, cands = LIVE_PMC['pm'], ['live: rocprofv3 --pmc passes run by this command']
-            else:
-                pm = json.load(open(os.path.join(ROOT, 'profiles', cands[-1])))
-                cands[-1] = 'static, ' + cands[-1]
-            if 'hbm_bytes_per_step' in pm and args.depth == 50 and args.dtype == 'bf16' and B == 256 \
-                    and not args.quantize and world == 1:
-                rate = pm['hbm_bytes_per_step'] / (elapsed / args.steps) / 1e9
-                out['hbm_measured_whole_step'] = {
-                    'traffic_gb_per_step': round(pm['hbm_bytes_per_step'] / 1e9, 1), 'rate_gbs': round(rate, 0),
-                    'frac_of_peak': round(rate / PEAK_HBM_GBS, 4),
-                    'frac_of_streaming_rate': round(rate / 5100.0, 4),
-                    'note': 'traffic: %s (all kernels of a step); streaming rate = 5100 GB/s (tools/bench_skew.py)'
-                            % cands[-1]}
-        except Exception:
-            pass
+        if args.full:
+            try:
+                cands = sorted((f for f in os.listdir(os.path.join(ROOT, 'profiles')) if f.endswith('pmc_traffic.json')),
+                                   key=_pmc_file_order)
+                if LIVE_PMC.get('pm') is not None:
+                    pm, cands = LIVE_PMC['pm'], ['live: rocprofv3 --pmc passes run by this command']
+                else:
+                    pm = json.load(open(os.path.join(ROOT, 'profiles', cands[-1])))
+                    cands[-1] = 'static, ' + cands[-1]
+                if 'hbm_bytes_per_step' in pm and args.depth == 50 and args.dtype == 'bf16' and B == 256 \
+                        and not args.quantize and world == 1:
+                    rate = pm['hbm_bytes_per_step'] / (elapsed / args.steps) / 1e9
+                    out['hbm_measured_whole_step'] = {
+                        'traffic_gb_per_step': round(pm['hbm_bytes_per_step'] / 1e9, 1), 'rate_gbs': round(rate, 0),
+                        'frac_of_peak': round(rate / PEAK_HBM_GBS, 4),
+                        'frac_of_streaming_rate': round(rate / 5100.0, 4),
+                        'note': 'traffic: %s (all kernels of a step); streaming rate = 5100 GB/s (tools/bench_skew.py)'
+                                % cands[-1]}
+            except Exception:
+                pass
         detail = {'kernels': kernels, 'kernels_overlapped': kernels_ovl, 'conv_layers': layers}
         if kernels:
             try:

@@ -9,10 +9,10 @@ if [ "$1" != "emul-only" ]; then
   # CN_EXTRA_FLAGS / CN_LIB_NAME: A/B builds (e.g. CN_EXTRA_FLAGS=-DCN_NT_STORES CN_LIB_NAME=libconvnet_hip_nt.so)
   LIB=${CN_LIB_NAME:-libconvnet_hip.so}
   # one object per source, compiled in parallel (igemm.hip alone is most of the serial build).  The object cache is
-  # keyed by THIS source directory and the extra flags (two checkouts or two A/B builds never share objects), and an
+  # keyed by THIS source directory, the extra flags and the user (two checkouts or two A/B builds never share objects), and an
   # object is reused only when the content hash of its source + every header it can see (csrc/*.h and the public
   # include/convnet_hip.h) + the flags equals the hash stored beside it - never on mtimes.
-  KEY=$(printf '%s|%s' "$(pwd -P)" "$CN_EXTRA_FLAGS" | sha1sum | cut -c1-12)
+  KEY=$(printf '%s|%s|%s' "$(pwd -P)" "$CN_EXTRA_FLAGS" "$(id -u)" | sha1sum | cut -c1-12)
   ODIR=${CN_OBJ_DIR:-/tmp/cn_hip_obj}_$KEY
   mkdir -p $ODIR
   HDRS=$(cat *.h ../../include/convnet_hip.h | sha1sum | cut -c1-40)
@@ -39,13 +39,18 @@ if [ "$1" != "emul-only" ]; then
 fi
 if [ "$1" = "emul" ] || [ "$1" = "emul-only" ]; then
   CXX=/opt/rocm/lib/llvm/bin/clang++
-  OBJS=""
+  # objects in a private directory: two checkouts or two users building at once never share (or own) each other's files
+  EDIR=$(mktemp -d "${TMPDIR:-/tmp}/cn_emul.XXXXXX")
+  trap 'rm -rf "$EDIR"' EXIT
+  pids=""
   for s in $SRCS; do
-    $CXX -x c++ -std=c++17 -O2 -fPIC -DCN_EMULATE -Wno-unused-result -Wno-shift-negative-value -c $s -o /tmp/cn_emul_${s%.hip}.o &
+    $CXX -x c++ -std=c++17 -O2 -fPIC -DCN_EMULATE -Wno-unused-result -Wno-shift-negative-value -c $s -o $EDIR/${s%.hip}.o &
+    pids="$pids $!"
   done
-  wait
-  for s in $SRCS; do OBJS="$OBJS /tmp/cn_emul_${s%.hip}.o"; done
-  $CXX -std=c++17 -O2 -fPIC -DCN_EMULATE -c cn_emul.cpp -o /tmp/cn_emul_rt.o
-  $CXX -shared -o $OUT/libconvnet_emul.so $OBJS /tmp/cn_emul_rt.o
+  for p in $pids; do wait $p || { echo "emulator build failed" >&2; exit 1; }; done
+  OBJS=""
+  for s in $SRCS; do OBJS="$OBJS $EDIR/${s%.hip}.o"; done
+  $CXX -std=c++17 -O2 -fPIC -DCN_EMULATE -c cn_emul.cpp -o $EDIR/rt.o
+  $CXX -shared -o $OUT/libconvnet_emul.so $OBJS $EDIR/rt.o
   echo "built $OUT/libconvnet_emul.so"
 fi

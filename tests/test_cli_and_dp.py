@@ -51,7 +51,9 @@ def test_cli_train_checkpoint_resume(mode, tmp_path):
     from oracle import convnet_oracle as O
     oracle = O.OracleResNet(18, 16, 8, (8, 16, 32, 64))
     oracle.load_state_dict(ck['state_dict'])
-    val = main(common + ['--save', 'ev', '-e', str(run / 'checkpoint.pth.tar')])
+    # evaluation saves under /tmp whatever --results-dir says (as the reference does): an absolute --save keeps the run
+    # inside this test's own directory instead of a fixed path that another user or run may already own
+    val = main(common + ['--save', str(tmp_path / 'ev'), '-e', str(run / 'checkpoint.pth.tar')])
     from convnet_amd.main import SyntheticLoader
     data = list(SyntheticLoader(1, 4, 32, 16, 3, 123 + 10000))
     ref = O.oracle_validate(oracle, data)

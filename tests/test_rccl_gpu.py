@@ -136,7 +136,7 @@ def test_bench_eight_rank_protocol_under_the_drivers_launcher(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr',
            '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '3',
-           '--warmup', '2', '--batch', '4', '--no-cpu-baseline', '--no-kernel-profile']
+           '--warmup', '2', '--batch', '4', '--full', '--no-cpu-baseline', '--no-kernel-profile']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.split('\n') if l.startswith('{"metric"')]

@@ -10,5 +10,5 @@ if [ "$KEXPR" != "-" ]; then
 fi
 echo "== A/B"; AB_STEPS=${AB_STEPS:-30} timeout 2400 python tools/gpu_ab.py $TAG $ROUNDS "$@" 2>&1 | tee $OUT/ab.txt
 if [ -n "$DETAIL_ENV" ]; then
-  echo "== detail ($DETAIL_ENV)"; env $DETAIL_ENV timeout 600 python bench.py --steps 10 --warmup 5 --no-cpu-baseline --detail-out $OUT/bench_detail.json | tail -c 300
+  echo "== detail ($DETAIL_ENV)"; env $DETAIL_ENV timeout 600 python bench.py --steps 10 --warmup 5 --full --no-cpu-baseline --detail-out $OUT/bench_detail.json | tail -c 300
 fi

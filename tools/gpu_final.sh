@@ -9,14 +9,14 @@ mkdir -p $OUT
   python -c "import sys;sys.path.insert(0,'.');from oracle.convnet_oracle import usable_cpus;print('usable cpus',usable_cpus())"; nproc; } > $OUT/env.txt 2>&1
 echo "== gpu tests"; timeout 2400 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider 2>&1 | tail -40 | tee $OUT/pytest_gpu.txt
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 | tee $OUT/smoke.txt
-echo "== bench (+pmc)"; timeout 1800 python bench.py --steps 20 --warmup 5 --pmc --pmc-out $OUT/pmc_traffic.json --detail-out $OUT/bench_detail.json 2> $OUT/bench.err | tail -1 > $OUT/bench.json; cut -c1-400 $OUT/bench.json; wc -c $OUT/bench.json; tail -3 $OUT/bench.err
+echo "== bench (+pmc)"; timeout 1800 python bench.py --steps 20 --warmup 5 --full --pmc --pmc-out $OUT/pmc_traffic.json --detail-out $OUT/bench_detail.json 2> $OUT/bench.err | tail -1 > $OUT/bench.json; cut -c1-400 $OUT/bench.json; wc -c $OUT/bench.json; tail -3 $OUT/bench.err
 echo "== layers"; timeout 600 python tools/bench_layers.py --variants 0 2>&1 | grep -v amdgpu.ids | tail -30 | tee $OUT/layers.txt
-echo "== b8"; timeout 300 python bench.py --batch 8 --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-profile 2>/dev/null | grep '"metric"' | tee $OUT/bench_b8.json | cut -c1-250
-echo "== host inputs"; timeout 300 python bench.py --host-inputs --steps 20 --warmup 5 --no-cpu-baseline --no-kernel-profile 2>/dev/null | grep '"metric"' | tee $OUT/bench_host_inputs.json | cut -c1-250
-echo "== world-1 RCCL"; BENCH_FORCE_DIST=1 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-profile 2>/dev/null | grep '"metric"' | tee $OUT/bench_dist1.json | cut -c1-300
-echo "== R18 fp32"; timeout 600 python bench.py --depth 18 --dtype f32 --steps 6 --warmup 4 --no-cpu-baseline 2>/dev/null | grep '"metric"' | tee $OUT/bench_r18_f32.json | cut -c1-250
-echo "== R101 bf16"; timeout 600 python bench.py --depth 101 --steps 20 --warmup 10 --no-cpu-baseline --no-kernel-profile 2>/dev/null | grep '"metric"' | tee $OUT/bench_r101.json | cut -c1-250
-echo "== config 5"; timeout 600 python bench.py --quantize --steps 6 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '"metric"' | tee $OUT/bench_config5.json | cut -c1-250
+echo "== b8"; timeout 300 python bench.py --batch 8 --steps 20 --warmup 5 --full --no-cpu-baseline --no-kernel-profile 2>/dev/null | grep '"metric"' | tee $OUT/bench_b8.json | cut -c1-250
+echo "== host inputs"; timeout 300 python bench.py --host-inputs --steps 20 --warmup 5 --full --no-cpu-baseline --no-kernel-profile 2>/dev/null | grep '"metric"' | tee $OUT/bench_host_inputs.json | cut -c1-250
+echo "== world-1 RCCL"; BENCH_FORCE_DIST=1 timeout 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-kernel-profile 2>/dev/null | grep '"metric"' | tee $OUT/bench_dist1.json | cut -c1-300
+echo "== R18 fp32"; timeout 600 python bench.py --depth 18 --dtype f32 --steps 6 --warmup 4 --full --no-cpu-baseline 2>/dev/null | grep '"metric"' | tee $OUT/bench_r18_f32.json | cut -c1-250
+echo "== R101 bf16"; timeout 600 python bench.py --depth 101 --steps 20 --warmup 10 --full --no-cpu-baseline --no-kernel-profile 2>/dev/null | grep '"metric"' | tee $OUT/bench_r101.json | cut -c1-250
+echo "== config 5"; timeout 600 python bench.py --quantize --steps 6 --warmup 3 --full --no-cpu-baseline 2>/dev/null | grep '"metric"' | tee $OUT/bench_config5.json | cut -c1-250
 echo "== rocprof"
 # (default flags: after four eager warm-up steps the traced steps are launch-plan replays - the shipped step)
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o r50 -- python bench.py --steps 6 --warmup 5 --no-cpu-baseline --no-kernel-profile > $OUT/rocprof.log 2>&1
