@@ -79,6 +79,11 @@ _SIGNATURES = {
     'cn_stem_wgrad': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_sz, c_p]),
     'cn_conv3x3_c64_ok': (c_i, [c_i] * 5),
     'cn_conv3x3_c64_rows': (c_i, [c_i, c_i]),
+    'cn_gconv2d_ok': (c_i, [c_i] * 10),
+    'cn_gconv2d_fwd': (c_i, [c_p, c_p, c_p] + [c_i] * 8 + [c_p]),
+    'cn_gconv2d_dgrad': (c_i, [c_p, c_p, c_p] + [c_i] * 8 + [c_p]),
+    'cn_gconv2d_wgrad_workspace': (c_sz, [c_i] * 8),
+    'cn_gconv2d_wgrad': (c_i, [c_p, c_p, c_p] + [c_i] * 8 + [c_f, c_f, c_p, c_sz, c_p]),
     'cn_conv3x3_c64': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
     'cn_conv1x1_stream_fwd_ok': (c_i, [c_i, c_i, c_i]),
     'cn_conv1x1_stream_fwd_rows': (c_i, [c_i] * 4),

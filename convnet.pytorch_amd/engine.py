@@ -120,10 +120,15 @@ class ParamArena(object):
             co, creal = mod.out_channels, mod.in_channels
             ch = 4 if dtype == torch.float32 else 8
             cpad = _round_up(creal, ch) if isinstance(mod, cnn.Conv2d) else creal
+            grouped = getattr(mod, 'groups', 1) > 1
+            if grouped:
+                # grouped filter [K][R][S][C/g]: the gconv kernels read the KRSC copy as it is (no channel padding)
+                # for the forward, the data gradient and the weight gradient; no CRSK copy
+                creal = cpad = mod.in_channels // mod.groups
             n = co * taps * cpad
             krsc_off = off
             off += _round_up(n, _ALIGN)
-            want_crsk = isinstance(mod, cnn.Linear) or (getattr(mod, 'needs_dgrad', True) and cpad == creal)
+            want_crsk = not grouped and (isinstance(mod, cnn.Linear) or (getattr(mod, 'needs_dgrad', True) and cpad == creal))
             crsk_off = -1
             if want_crsk:
                 crsk_off = off

@@ -54,7 +54,7 @@ class ResidualBlock(tnn.Module):
     """BasicBlock / Bottleneck of the reference (models/resnet.py:81-165) built from a branch plan.
     The last BN of the branch fuses `+ residual` and the final ReLU; inner BNs fuse their ReLU."""
 
-    def __init__(self, kind, inplanes, planes, stride, expansion, downsample, op_classes=None):
+    def __init__(self, kind, inplanes, planes, stride, expansion, downsample, op_classes=None, groups=1):
         super().__init__()
         self.kind = kind
         self.quantized = op_classes is not None
@@ -62,16 +62,21 @@ class ResidualBlock(tnn.Module):
         widths = {'planes': planes, 'out': planes * expansion}
         cin = inplanes
         self.n_convs = len(_BRANCH[kind])
+        # groups > 1 (ResNeXt): every 3x3 convolution of the branch is grouped (the reference's conv3x3(..., groups)).
+        # A grouped convolution takes part in no fusion: the BatchNorm it feeds runs its standalone passes, and no
+        # BatchNorm parks a lazy operand (or its backward reduction) on it; everything else keeps its fusions.
+        self.grouped = [k == 3 and groups > 1 for k, _, _ in _BRANCH[kind]]
         for i, (k, wkey, strided) in enumerate(_BRANCH[kind], start=1):
             cout = widths[wkey]
+            gkw = {'groups': groups} if self.grouped[i - 1] else {}
             setattr(self, 'conv%d' % i, Conv(cin, cout, kernel_size=k, stride=stride if strided else 1,
-                                             padding=k // 2, bias=False))
+                                             padding=k // 2, bias=False, **gkw))
             setattr(self, 'bn%d' % i, Norm(cout))
-            if not self.quantized:
+            if not self.quantized and not self.grouped[i - 1]:
                 getattr(self, 'conv%d' % i).feeds_batchnorm = True   # BN statistics come out of the conv epilogue
                 getattr(self, 'conv%d' % i).__dict__['stats_bn'] = getattr(self, 'bn%d' % i)   # ... centred on its running mean
                 getattr(self, 'bn%d' % i).__dict__['producer_conv'] = getattr(self, 'conv%d' % i)   # (lazy dy: ops.LAZY_DY)
-            if i > 1 and not self.quantized:   # this conv reads relu(bn_{i-1}(.)): its dgrad epilogue does that BN's backward reduction
+            if i > 1 and not self.quantized and not self.grouped[i - 1] and not self.grouped[i - 2]:   # this conv reads relu(bn_{i-1}(.)): its dgrad epilogue does that BN's backward reduction
                 # (instance dict, not setattr: the BN must not become a registered sub-module of the conv)
                 getattr(self, 'conv%d' % i).__dict__['input_bn'] = getattr(self, 'bn%d' % (i - 1))
             if i == 1 and kind == 'basic':
@@ -99,6 +104,14 @@ class ResidualBlock(tnn.Module):
                 self.conv1.__dict__['share_q_out'] = True
                 downsample[0].__dict__['share_q_from'] = self.conv1
             return
+        if self.grouped[0]:
+            # conv1 is grouped (ResNeXt BasicBlock): the two gradients meeting at the block input are added by the fork
+            self._holder = None
+            if downsample is not None:
+                downsample[0].feeds_batchnorm = True
+                downsample[0].__dict__['stats_bn'] = downsample[1]
+                downsample[1].__dict__['producer_conv'] = downsample[0]
+            return
         # the two gradients meeting at the block input are summed inside a dgrad epilogue
         from ..ops import ResGradHolder
         self._holder = ResGradHolder()
@@ -120,6 +133,8 @@ class ResidualBlock(tnn.Module):
         convolution on the 64-channel halo kernel applies that BatchNorm on its operand path (ops.LAZY_A)."""
         if not self.quantized:
             for i in range(1, self.n_convs):
+                if self.grouped[i - 1] or self.grouped[i]:
+                    continue
                 getattr(self, 'bn%d' % i).__dict__['inner_consumer_conv'] = getattr(self, 'conv%d' % (i + 1))
 
     def set_input_bn(self, bn):
@@ -127,10 +142,12 @@ class ResidualBlock(tnn.Module):
         whichever of conv1 / downsample conv completes the input gradient reduces it for that BN."""
         if self.quantized:
             return
-        self.conv1.__dict__['input_bn'] = bn
-        bn.__dict__['consumer_conv'] = self.conv1   # (lazy z: conv1 can apply that junction on its operand load, ops.LAZY_Z)
         if self.downsample is not None:
             self.downsample[0].__dict__['input_bn'] = bn
+        if self.grouped[0]:
+            return
+        self.conv1.__dict__['input_bn'] = bn
+        bn.__dict__['consumer_conv'] = self.conv1   # (lazy z: conv1 can apply that junction on its operand load, ops.LAZY_Z)
 
     def forward(self, x):
         xa, xb = cnn.fork(x, self._holder)
@@ -180,8 +197,15 @@ class ResNetImagenet(tnn.Module):
 
     def __init__(self, num_classes=1000, inplanes=64, block='bottleneck', layers=(3, 4, 23, 3),
                  width=(64, 128, 256, 512), expansion=4, regime='normal', scale_lr=1, ramp_up_lr=True,
-                 ramp_up_epochs=5, epochs=90, base_devices=4, base_device_batch=64, quantize=False):
+                 ramp_up_epochs=5, epochs=90, base_devices=4, base_device_batch=64, quantize=False,
+                 groups=(1, 1, 1, 1)):
         super().__init__()
+        groups = [int(g) for g in groups]
+        if len(groups) != len(layers) or min(groups) < 1:
+            raise ValueError('groups must give one positive group count per stage, got %r' % (groups,))
+        if quantize and max(groups) > 1:
+            raise NotImplementedError('quantize=True with grouped convolutions (groups=%r): the quantised operators are '
+                                      'dense-only' % (groups,))
         self.inplanes = inplanes
         self.op_classes = None
         if quantize:
@@ -198,7 +222,7 @@ class ResNetImagenet(tnn.Module):
         self.maxpool = cnn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         for i, nblocks in enumerate(layers):
             setattr(self, 'layer%d' % (i + 1),
-                    self._make_layer(block, width[i], nblocks, expansion, stride=1 if i == 0 else 2))
+                    self._make_layer(block, width[i], nblocks, expansion, stride=1 if i == 0 else 2, groups=groups[i]))
         prev = None
         for m in self.modules():   # registration order = execution order of the residual blocks
             if isinstance(m, ResidualBlock):
@@ -246,7 +270,7 @@ class ResNetImagenet(tnn.Module):
             self.regime[0]['step_lambda'] = linear_scale(0.1, 0.1 * scale_lr, ramp_up_steps)
             self.regime.insert(1, {'epoch': ramp_up_epochs, 'lr': scale_lr * 1e-1})
 
-    def _make_layer(self, kind, planes, blocks, expansion, stride):
+    def _make_layer(self, kind, planes, blocks, expansion, stride, groups=1):
         out_planes = planes * expansion
         downsample = None
         if stride != 1 or self.inplanes != out_planes:  # models/resnet.py:176-181
@@ -254,10 +278,10 @@ class ResNetImagenet(tnn.Module):
             downsample = tnn.Sequential(
                 Conv(self.inplanes, out_planes, kernel_size=1, stride=stride, bias=False),
                 Norm(out_planes))
-        stage = [ResidualBlock(kind, self.inplanes, planes, stride, expansion, downsample, self.op_classes)]
+        stage = [ResidualBlock(kind, self.inplanes, planes, stride, expansion, downsample, self.op_classes, groups)]
         self.inplanes = out_planes
         for _ in range(1, blocks):
-            stage.append(ResidualBlock(kind, self.inplanes, planes, 1, expansion, None, self.op_classes))
+            stage.append(ResidualBlock(kind, self.inplanes, planes, 1, expansion, None, self.op_classes, groups))
         return tnn.Sequential(*stage)
 
     def features(self, x):
@@ -287,7 +311,8 @@ class ResNetImagenet(tnn.Module):
 
 
 def resnet(**config):
-    """Factory with the reference's call shape: resnet(dataset=..., depth=..., **kw)."""
+    """Factory with the reference's call shape: resnet(dataset=..., depth=..., **kw); groups=[g1, g2, g3, g4] makes
+    every 3x3 convolution of stage i grouped (the reference's ResNet_imagenet(groups=...), ResNeXt's building block)."""
     dataset = config.pop('dataset', 'imagenet')
     if config.pop('bn_norm', None):
         raise NotImplementedError("resnet(bn_norm=...) is not part of the MI355X hot path")

@@ -57,25 +57,37 @@ class _ArenaModule(tnn.Module):
 
 
 class Conv2d(_ArenaModule):
-    """nn.Conv2d(in, out, kernel_size, stride, padding, dilation, groups, bias) - groups=1,
-    dilation=1 (all that models/resnet.py and models/mnist.py use)."""
+    """nn.Conv2d(in, out, kernel_size, stride, padding, dilation, groups, bias) - dilation=1; groups > 1 only as the
+    grouped 3x3 convolution of a ResNeXt block (3x3, stride 1 or 2, padding 1, no bias, 1 <= C/g, K/g <= 64:
+    ops.GroupedConv2dFunction on csrc/gconv.hip)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
                  bias=True, padding_mode='zeros'):
         super().__init__()
-        if groups != 1 or _pair(dilation) != (1, 1) or padding_mode != 'zeros':
-            raise NotImplementedError('HIP Conv2d supports groups=1, dilation=1, zero padding')
+        if _pair(dilation) != (1, 1) or padding_mode != 'zeros':
+            raise NotImplementedError('HIP Conv2d supports dilation=1, zero padding')
+        if groups != 1:
+            ok = (groups > 1 and in_channels % groups == 0 and out_channels % groups == 0
+                  and 1 <= in_channels // groups <= 64 and 1 <= out_channels // groups <= 64
+                  and _pair(kernel_size) == (3, 3) and _pair(stride) in ((1, 1), (2, 2)) and _pair(padding) == (1, 1)
+                  and not bias)
+            if not ok:
+                raise NotImplementedError(
+                    'HIP Conv2d supports groups > 1 only as a 3x3 / stride 1 or 2 / padding 1 convolution without bias '
+                    'whose groups divide in and out channels with 1 <= channels per group <= 64 (got in=%d out=%d '
+                    'kernel=%s stride=%s padding=%s groups=%d bias=%s)'
+                    % (in_channels, out_channels, kernel_size, stride, padding, groups, bias))
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.padding = _pair(kernel_size), _pair(stride), _pair(padding)
-        self.dilation, self.groups = (1, 1), 1
+        self.dilation, self.groups = (1, 1), groups
         self.out_f32 = False
         # same RNG consumption as torch.nn.Conv2d.reset_parameters so that seeded model
         # construction reproduces the reference's initial weights bit for bit
-        self.weight = tnn.Parameter(torch.empty(out_channels, in_channels, *self.kernel_size))
+        self.weight = tnn.Parameter(torch.empty(out_channels, in_channels // groups, *self.kernel_size))
         init.kaiming_uniform_(self.weight, a=math.sqrt(5))
         if bias:
             self.bias = tnn.Parameter(torch.empty(out_channels))
-            fan_in = in_channels * self.kernel_size[0] * self.kernel_size[1]
+            fan_in = in_channels // groups * self.kernel_size[0] * self.kernel_size[1]
             bound = 1 / math.sqrt(fan_in) if fan_in > 0 else 0
             init.uniform_(self.bias, -bound, bound)
         else:
@@ -96,6 +108,15 @@ class Conv2d(_ArenaModule):
 
     def forward(self, x):
         self._require_prepared()
+        if self.groups > 1:
+            if x.shape[-1] != self.in_channels:
+                raise _lib.ConvNetHipError('grouped Conv2d expected %d NHWC channels, got %s'
+                                           % (self.in_channels, tuple(x.shape)))
+            if not ops.gconv2d_ok(self.in_channels, self.out_channels, self.groups, self.kernel_size, self.stride,
+                                  self.padding, x.dtype):
+                raise NotImplementedError('grouped Conv2d %d -> %d (groups %d) in %s: channels must be multiples of the '
+                                          'dtype\'s chunk' % (self.in_channels, self.out_channels, self.groups, x.dtype))
+            return ops.GroupedConv2dFunction.apply(x, self.weight, self)
         if x.shape[-1] != self.padded_in_channels():
             raise _lib.ConvNetHipError('Conv2d expected %d (padded) NHWC channels, got %s'
                                        % (self.padded_in_channels(), tuple(x.shape)))
@@ -126,9 +147,9 @@ class Conv2d(_ArenaModule):
         return self.forward(ops.nchw_to_nhwc(x_nchw, self.compute_dtype, self.padded_in_channels()))
 
     def extra_repr(self):
-        return '{}, {}, kernel_size={}, stride={}, padding={}, bias={}'.format(
+        return '{}, {}, kernel_size={}, stride={}, padding={}{}, bias={}'.format(
             self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding,
-            self.bias is not None)
+            ', groups={}'.format(self.groups) if self.groups != 1 else '', self.bias is not None)
 
 
 class Linear(_ArenaModule):

@@ -653,6 +653,51 @@ def conv2d_bwd1x1_lazy(x, g, bn_y, coef, w_crsk, dw_krsc, K, beta=1.0, scale=1.0
     return dx
 
 
+# grouped 3x3 convolutions (csrc/gconv.hip): filter w [K][3][3][C/g] in the compute dtype (the KRSC copy), stride 1 or 2,
+# padding 1.  FLOPs are the true grouped ones (2 * 9 * C/g per output element), bytes the algorithmic traffic.
+def gconv2d_ok(C, K, groups, kernel_size, stride, padding, dtype):
+    return bool(_L().cn_gconv2d_ok(C, K, groups, kernel_size[0], kernel_size[1], stride[0], stride[1], padding[0],
+                                   padding[1], dtype_code(dtype)))
+
+
+def gconv2d_fwd(x, w, K, groups, stride):
+    N, H, W, C = x.shape
+    P, Q = conv_out_hw(H, W, 3, 3, (stride, stride), (1, 1))
+    y = torch.empty((N, P, Q, K), dtype=x.dtype, device=x.device)
+    cg = C // groups
+    PROFILER.run(_last_kernel(), 1, 2.0 * N * P * Q * K * 9 * cg,
+                 x.numel() * _esize(x) + y.numel() * _esize(y) + K * 9 * cg * _esize(x),
+                 lambda: check(_L().cn_gconv2d_fwd(ptr(x), ptr(w), ptr(y), N, H, W, C, K, groups, stride,
+                                                   dtype_code(x.dtype), stream_of(x)), 'cn_gconv2d_fwd'),
+                 x.device, detail=_conv_detail('gfwd', C, H, K, 3, (stride, stride)))
+    return y
+
+
+def gconv2d_dgrad(dy, w, x_shape, K, groups, stride):
+    N, H, W, C = x_shape
+    dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+    PROFILER.run(_last_kernel(), 1, 2.0 * dy.numel() * 9 * (C // groups),
+                 dy.numel() * _esize(dy) + dx.numel() * _esize(dx) + K * 9 * (C // groups) * _esize(dy),
+                 lambda: check(_L().cn_gconv2d_dgrad(ptr(dy), ptr(w), ptr(dx), N, H, W, C, K, groups, stride,
+                                                     dtype_code(dy.dtype), stream_of(dy)), 'cn_gconv2d_dgrad'),
+                 dy.device, detail=_conv_detail('gdgrad', C, H, K, 3, (stride, stride)))
+    return dx
+
+
+def gconv2d_wgrad(x, dy, dw, K, groups, stride, beta=1.0, scale=1.0, tag='main'):
+    """dw (fp32, [K][3][3][C/g] memory order) = beta*dw + scale*wgrad."""
+    N, H, W, C = x.shape
+    code = dtype_code(x.dtype)
+    L = _L()
+    need = L.cn_gconv2d_wgrad_workspace(N, H, W, C, K, groups, stride, code)
+    ws = workspace(need, x.device, tag)
+    PROFILER.run(_last_kernel(), 2, 2.0 * dy.numel() * 9 * (C // groups),
+                 x.numel() * _esize(x) + dy.numel() * _esize(dy) + 2.0 * need + K * 9 * (C // groups) * 4,
+                 lambda: check(L.cn_gconv2d_wgrad(ptr(x), ptr(dy), ptr(dw), N, H, W, C, K, groups, stride, code, beta,
+                                                  scale, ptr(ws), ws.numel() * 4, stream_of(x)), 'cn_gconv2d_wgrad'),
+                 x.device, detail=_conv_detail('gwgrad', C, H, K, 3, (stride, stride)))
+
+
 def weight_prep(w_master_krsc, w_krsc, w_crsk, Co, taps, c_real, c_pad):
     PROFILER.run('weight_prep', 1, 0.0, Co * taps * c_real * 4 + Co * taps * c_pad * _esize(w_krsc) * (2 if w_crsk is not None else 1),
                  lambda: check(_L().cn_weight_prep(ptr(w_master_krsc), ptr(w_krsc), ptr(w_crsk), Co, taps, c_real,
@@ -969,6 +1014,49 @@ class Conv2dFunction(Function):
         if DGRAD_FIRST:
             submit_wgrad()
         return out
+
+
+class GroupedConv2dFunction(Function):
+    """A grouped 3x3 convolution (ResNeXt's conv2).  It takes part in no fusion: no BatchNorm statistics in its epilogue,
+    no lazy operands, no junction pairing - the BatchNorms beside it run their standalone passes.  The weight gradient
+    goes to the side stream exactly like Conv2dFunction's."""
+    @staticmethod
+    def forward(ctx, x, weight, mod):
+        mod.ensure_prepared()
+        if mod.__dict__.get('_lazy_z') is not None or mod.__dict__.get('_lazy_a') is not None:
+            raise _lib.ConvNetHipError('grouped convolution: a lazy operand was parked for it (grouped convs take no fusion)')
+        y = gconv2d_fwd(x, mod.w_krsc, mod.out_channels, mod.groups, mod.stride[0])
+        ctx.mod = mod
+        ctx.save_for_backward(x)
+        mod._lazy_dy = None
+        COUNTERS['gconv'] = COUNTERS.get('gconv', 0) + 1
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        mod = ctx.mod
+        if getattr(mod, '_lazy_dy', None) is not None or _is_zero_placeholder(dy):
+            raise _lib.ConvNetHipError('grouped convolution: a lazy gradient reached it (grouped convs take no fusion)')
+        dy = dy.contiguous()
+        K, g, st = mod.out_channels, mod.groups, mod.stride[0]
+
+        def submit_wgrad():
+            if SIDE.active(x):
+                def launch():
+                    gconv2d_wgrad(x, dy, mod.grad_view('weight'), K, g, st, tag='side')
+                    return (x, dy)
+                SIDE.submit(x.device, launch, mod._notify_grad_ready, dy)
+            else:
+                gconv2d_wgrad(x, dy, mod.grad_view('weight'), K, g, st)
+                mod._notify_grad_ready()
+
+        if not DGRAD_FIRST:
+            submit_wgrad()
+        dx = gconv2d_dgrad(dy, mod.w_krsc, x.shape, K, g, st) if ctx.needs_input_grad[0] else None
+        if DGRAD_FIRST:
+            submit_wgrad()
+        return dx, None, None
 
 
 def _sync_group(mod):

@@ -212,6 +212,23 @@ int cn_conv2d_dgrad_junction_rows_k(int N, int H, int W, int C, int K);   /* ...
 int cn_conv2d_dgrad_junction(const void* dy, const void* w_crsk, void* g, const void* addend, int addend_sub, int N, int H,
                              int W, int C, int K, int dtype, const void* bn_y, const unsigned char* bn_mask,
                              const float* bn_coef, float* partial, int partial_rows, void* stream);
+/* Grouped 3x3 convolution, stride 1 or 2, padding 1 (the conv3x3 of a ResNeXt block, /root/reference
+ * models/resnet.py:75-78 with groups > 1) on MFMA as block-diagonal products (csrc/gconv.hip).  NHWC activations in the
+ * compute dtype, filter w[K][3][3][C/g] in the compute dtype (the KRSC copy of cn_weight_prep), fp32 accumulation.
+ *   fwd:   y[N][P][Q][K] = conv(x[N][H][W][C], w), P = (H - 1) / stride + 1
+ *   dgrad: dx[N][H][W][C] from dy[N][P][Q][K] and the same filter
+ *   wgrad: dw[K][3][3][C/g] (fp32) = beta*dw + scale*wgrad(x, dy); split reduction through `workspace`
+ *          (cn_gconv2d_wgrad_workspace bytes), fixed summation order.
+ * cn_gconv2d_ok: groups divide C and K, 1 <= C/g, K/g <= 64, C and K multiples of the dtype's chunk, 3x3, equal strides of
+ * 1 or 2, padding 1; every other configuration is refused with CN_ESHAPE. */
+int cn_gconv2d_ok(int C, int K, int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dtype);
+int cn_gconv2d_fwd(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int groups, int stride,
+                   int dtype, void* stream);
+int cn_gconv2d_dgrad(const void* dy, const void* w, void* dx, int N, int H, int W, int C, int K, int groups, int stride,
+                     int dtype, void* stream);
+size_t cn_gconv2d_wgrad_workspace(int N, int H, int W, int C, int K, int groups, int stride, int dtype);
+int cn_gconv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int groups, int stride,
+                     int dtype, float beta, float scale, void* workspace, size_t ws_bytes, void* stream);
 /* dw[K,R,S,C_real] (fp32) = beta*dw + scale * sum_pixels dy (x) x ; split reduction through
  * `workspace` (cn_conv2d_wgrad_workspace bytes), fixed summation order. */
 size_t cn_conv2d_wgrad_workspace(int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
