@@ -223,8 +223,29 @@ class SideStream(object):
         self._held.clear()     # (what the current stream does from here on is ordered behind the side stream's reads)
         self._held_bytes = 0
 
+    def reset(self):
+        """Forget the step in flight without waiting for it (an aborted capture: nothing was queued)."""
+        self._held.clear()
+        self._held_bytes, self.used, self._mark = 0, False, None
+
 
 SIDE = SideStream()
+
+
+def reset_step_state(model):
+    """An aborted step body (a capture that failed half way) leaves the per-step mailboxes half filled: empty them, the
+    next (eager) step starts clean.  Every mailbox of a step is cleared by the module that owns it."""
+    for m in model.modules():
+        h = getattr(m, '_res_holder', None)
+        if h is not None:
+            h.reset()
+        m.__dict__.pop('_lazy_z', None)
+        m.__dict__.pop('_lazy_a', None)
+        if hasattr(m, '_lazy_dy'):
+            m._lazy_dy = None
+    SIDE.reset()
+    from . import quant
+    quant.reset_step_state()
 
 
 def _esize(t):
@@ -1654,6 +1675,9 @@ class ResGradHolder(object):
     __slots__ = ('dres', 'fused', 'sub')   # sub = 2: dres holds only the even (h, w) pixels (stride-2 1x1 projection)
 
     def __init__(self):
+        self.reset()
+
+    def reset(self):
         self.dres, self.fused, self.sub = None, False, 1
 
 

@@ -59,6 +59,11 @@ QP_FROM_PRODUCER = flags.on('quant_qp_from_producer')
 _MM_STASH = {}
 
 
+def reset_step_state():
+    """Drop what an aborted step stashed (ops.reset_step_state)."""
+    _MM_STASH.clear()
+
+
 def _stash_minmax(t, rows, mm, uses=1, qp_extreme=None):
     """qp_extreme: [zero_point, range] of the 'extreme' reduction of mm (what a GRADIENT quantiser derives from it), when the
     producer's final kernel emitted it too."""

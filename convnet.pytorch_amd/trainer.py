@@ -28,6 +28,7 @@ from . import _lib, engine, flags, ops
 from ._lib import check, ptr, stream_of
 from .cross_entropy import CrossEntropyLoss
 from .meters import AverageMeter, accuracy
+from .step_policy import (CAPTURE_GRAPH, CAPTURE_PLAN, EAGER, EAGER_TIMED, REPLAY_TIMED, StepPolicy)
 
 
 class DevicePrefetcher(object):
@@ -266,9 +267,9 @@ class Trainer(object):
         # plan can be built it is what runs after the warm-up steps, whatever the batch size: it costs the host ~1 ms
         # per step instead of 11-12 ms and keeps the eager step's two-stream schedule (a replayed HIP graph does not).
         self._plan = flags.on('plan')
-        self._gstates = {}               # per (shapes, step options) key: {'seen': warm-up / timing bookkeeping, 'graph': capture}
-        self._graph_eager_for = set()    # (shapes, chunking) for which auto mode settled on eager launches
-        self._watch = {}                 # key -> EagerWatch: the eager verdict is re-examined while it is in force
+        # per (shapes, step options) key: {'policy': StepPolicy (how the step is issued: every decision and what it was
+        # based on), 'graph': the capture or None, 'watch': the EagerWatch of a watched eager verdict or None}
+        self._gstates = {}
         from . import nn as cnn
         # a captured step replays the SAME kernels: host-drawn Dropout masks (models/mnist.py) rule it out
         # modules whose capturability can change at run time (quant.QuantMeasure.no_graph follows the noise source) are
@@ -313,14 +314,12 @@ class Trainer(object):
             # configurations for which auto mode already settled on eager launches go straight to the eager body (the
             # bookkeeping of _graph_step costs a nearly host-bound step 1 %); the verdict is keyed like the graphs are
             key = self._graph_key(inputs_batch, target_batch, chunk_batch)
-            if key not in self._graph_eager_for:
+            rec = self._gstates.get(key)
+            if rec is None or not rec['policy'].eager:
                 if self._graph_ok(inputs_batch, target_batch):
-                    return self._graph_step(inputs_batch, target_batch, chunk_batch)
-            elif key in self._watch and not ops.PROFILER.enabled:
-                res = self._body(inputs_batch, target_batch, training, chunk_batch)
-                if self._watch[key].step(torch.cuda.current_stream(self.device), self._data_wait_ms):
-                    self._eager_verdict_withdrawn(key)
-                return res
+                    return self._graph_step(inputs_batch, target_batch, chunk_batch, key)
+            elif rec['policy'].watched and not ops.PROFILER.enabled:
+                return self._watched_eager_step(rec, inputs_batch, target_batch, chunk_batch)
         return self._body(inputs_batch, target_batch, training, chunk_batch)
 
     def _body(self, inputs_batch, target_batch, training, chunk_batch):
@@ -413,152 +412,118 @@ class Trainer(object):
         return (tuple(inputs.shape), tuple(target.shape), chunk_batch, float(self.grad_clip), self.loss_scale,
                 self.grad_scale, self.optimizer.runs_signature(), getattr(self.criterion, 'smooth_eps', None), self.world_size)
 
-    def _graph_step(self, inputs, target, chunk_batch):
+    def _record(self, key):
+        """The record of `key`, moved to the most recently used end.  Captures own a memory pool, so at most 4 keys are
+        kept on their way to a capture or with one, least recently USED out (a hit re-inserts its key at the end, so the hot
+        full-batch capture is never the one evicted); a record under an eager verdict holds no capture and stays."""
+        rec = self._gstates.pop(key, None)
+        if rec is None:
+            self._make_room()
+            rec = {'policy': StepPolicy(self._graph_mode, self._plan, self.reducer is None or self._graph_dp),
+                   'graph': None, 'watch': None}
+        self._gstates[key] = rec
+        return rec
+
+    def _make_room(self):
+        """... for one more key that is not under an eager verdict."""
+        live = [k for k, r in self._gstates.items() if not r['policy'].eager]
+        for k in live[:max(0, len(live) - 3)]:
+            del self._gstates[k]
+
+    def _graph_step(self, inputs, target, chunk_batch, key):
         """State is kept PER KEY (batch shapes + step options): the odd-shaped last batch of an epoch warms up /
         runs eagerly under its own key and leaves the captured full-batch graph alone (a single slot
-        used to be discarded and rebuilt every epoch).  NOTE: the (output, loss, grad-norm) a replay returns are
-        the graph's STATIC buffers - the next replay of the same graph overwrites them; Trainer.forward folds them
-        into the device meters right away, other callers must clone what they keep."""
-        opt = self.optimizer
-        opt.push_hyper()
-        key = self._graph_key(inputs, target, chunk_batch)
-        gs = self._gstates.pop(key, None)
-        if gs is None:
-            if len(self._gstates) >= 4:      # bounded, least recently USED out (a hit re-inserts its key at the end, so
-                self._gstates.pop(next(iter(self._gstates)))   # the hot full-batch graph is never the one evicted)
-            gs = {'seen': {'n': 0}, 'graph': None}
-        self._gstates[key] = gs
-        seen = gs['seen']
-        st = gs['graph']
-        eager_key = key      # an 'eager' verdict holds for exactly the configuration it was measured on
-        if st is None:
-            # eager warm-up steps before the capture: 4 when the host-vs-device timing of the last one decides between eager
-            # launches and a HIP graph (the first steps still grow workspaces and the allocator's pools); 2 when a launch plan
-            # follows whatever the timing says - the step then runs as a plan from the THIRD step on, so that a benchmark's
-            # warm-up of >= 3 steps leaves only replays in its timed region
-            warm = 2 if (self._graph_mode != 'auto' or self._plan) else 4
-            if seen['n'] < warm:       # eager warm-up (lazy workspace growth, allocator warm)
-                seen['n'] += 1
-                if seen['n'] < warm or self._graph_mode != 'auto':
-                    return self._body(inputs, target, True, chunk_batch)
-                # last warm-up step, mode 'auto' (the fourth: the first ones still grow workspaces and the allocator's
-                # pools): is the eager step bound by the host (launch time ~ device
-                # time) or by the device?  A replayed graph removes the host cost but measured 5 % SLOWER than the
-                # eager two-stream schedule when the device is the limit (ResNet-50 b=256: 22.1 vs 21.0 ms), and
-                # 1.55x faster when the host is (b=8: 5.5 vs 8.6 ms) - profiles/README.md.
-                torch.cuda.synchronize(self.device)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0 = time.perf_counter()
-                e0.record()
-                res = self._body(inputs, target, True, chunk_batch)
-                e1.record()
-                host_ms = (time.perf_counter() - t0) * 1e3
-                e1.synchronize()
-                dev_ms = e0.elapsed_time(e1)
-                seen['host_bound'] = host_ms > 0.75 * dev_ms
-                seen['plan'] = self._plan
-                seen['use'] = seen['plan'] or seen['host_bound']
-                seen['eager_ms'] = dev_ms
-                if not seen['use']:
-                    self._graph_eager_for.add(eager_key)
-                    self._watch[eager_key] = EagerWatch(dev_ms)
-                logging.debug('step: host %.2f ms, device %.2f ms -> %s', host_ms, dev_ms,
-                              'try a HIP graph' if seen['use'] else 'eager launches')
-                return res
-            if not seen.get('use', True):
+        used to be discarded and rebuilt every epoch).  What the step does is the StepPolicy's decision
+        (step_policy.py holds the table); this method carries it out.  NOTE: the (output, loss, grad-norm) a replay
+        returns are the capture's STATIC buffers - the next replay of the same capture overwrites them; Trainer.forward
+        folds them into the device meters right away, other callers must clone what they keep."""
+        self.optimizer.push_hyper()
+        rec = self._record(key)
+        pol = rec['policy']
+        act = pol.next_action()
+        if act is EAGER:           # warm-up (lazy workspace growth, allocator warm)
+            res = self._body(inputs, target, True, chunk_batch)
+            pol.eager_done()
+            return res
+        if act is EAGER_TIMED:
+            res, host_ms, dev_ms = self._timed(lambda: self._body(inputs, target, True, chunk_batch))
+            pol.eager_timed(host_ms, dev_ms)
+            logging.debug('step: host %.2f ms, device %.2f ms -> %s', host_ms, dev_ms,
+                          'eager launches' if pol.eager else 'try a HIP graph')
+            return res
+        if act in (CAPTURE_PLAN, CAPTURE_GRAPH):
+            if not self._capture_for(rec, inputs, target, chunk_batch, key):
                 return self._body(inputs, target, True, chunk_batch)
-            try:
-                try:
-                    st = gs['graph'] = self._capture(inputs, target, chunk_batch, key,
-                                                     plan=seen.get('plan', self._plan))
-                except PlanRefused as e:
-                    # the step holds something a plan cannot re-issue: the HIP graph (when the host is the limit and
-                    # nothing but this library's kernels would be captured) or eager launches serve it
-                    logging.warning('launch plan refused (%s): %s', e, 'HIP graph / eager launches instead')
-                    seen['plan'] = False
-                    if self._graph_mode == 'auto':
-                        seen['use'] = seen.get('host_bound', False)
-                    if self.reducer is not None and not self._graph_dp:
-                        seen['use'] = False
-                    if not seen['use']:
-                        self._graph_eager_for.add(eager_key)
-                        if 'eager_ms' in seen:
-                            self._watch[eager_key] = EagerWatch(seen['eager_ms'])
-                        return self._body(inputs, target, True, chunk_batch)
-                    st = gs['graph'] = self._capture(inputs, target, chunk_batch, key, plan=False)
-            except RuntimeError as e:      # (torch.cuda.OutOfMemoryError is one)
-                # A capture needs its own pool for the step's tensors, next to the blocks the eager steps keep cached.  When
-                # the capture was the WATCH's idea (a verdict withdrawn after many eager steps) and it does not fit, the
-                # configuration simply stays eager; a capture the configuration started with fails as it always did.
-                # The same holds for a launch-plan recording in graph = auto: the plan is an optimisation of a step that already
-                # ran eagerly twice - whatever made its capture fail (memory, a runtime that refuses the capture with the
-                # communicators of a multi-rank job alive, ...) must not take the job down.  graph = 1 asked for a capture
-                # and still gets the error.
-                if not (seen.get('withdrawn') or (seen.get('plan') and self._graph_mode == 'auto')):
-                    raise
-                logging.warning('capture of the training step failed (%s): staying with eager launches',
-                                str(e).split('\n')[0][:200])
-                seen['plan'] = False
-                if 'eager_ms' in seen and not seen.get('withdrawn'):
-                    self._watch[eager_key] = EagerWatch(seen['eager_ms'])
-                gs['graph'] = None
-                seen['use'] = False
-                self._graph_eager_for.add(eager_key)
-                torch.cuda.empty_cache()
-                return self._body(inputs, target, True, chunk_batch)
+            act = pol.next_action()
+        st = rec['graph']
         self._feed(st, inputs, target)
-        if self._graph_mode == 'auto' and 'graph_ms' not in seen and 'eager_ms' in seen:
-            # the prediction above is checked once: a nearly host-bound eager step can still beat the replay
-            # (ResNet-50 b=128: 12.2 ms eager vs 13.3 ms replayed), so the second replay is timed and the graph
-            # dropped if it is not faster than the eager step it was meant to replace
-            n = seen.get('replays', 0)
-            seen['replays'] = n + 1
-            if n == 1:
-                torch.cuda.synchronize(self.device)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                self._replay(st)
-                e1.record()
-                e1.synchronize()
-                seen['graph_ms'] = e0.elapsed_time(e1)
-                # (a plan is the eager schedule minus the host - the same launches on the same streams: it cannot be slower by
-                # construction, and this ONE sample also sees whatever else is on the device at that moment, e.g. the loader's
-                # host-to-device copy of the next batch (a plan was dropped that way in a --host-inputs run).  It is given up
-                # only when it measures grossly slower; what it buys - independence from the host's load - no quiet-box
-                # comparison can show)
-                if seen['graph_ms'] > (1.25 if st.get('plan') else 0.98) * seen['eager_ms']:
-                    seen['use'] = False
-                    self._graph_eager_for.add(eager_key)
-                    logging.debug('replayed step %.2f ms vs eager %.2f ms -> eager launches from now on',
-                                  seen['graph_ms'], seen['eager_ms'])
-                out, loss, grad = st['out'], st['loss'], st['grad']
-                self.arena.bump_version()
-                self.training_steps += 1
-                if not seen['use']:
-                    out = out.clone()
-                    loss = loss.clone()
-                    grad = grad.clone() if grad is not None else None
-                    gs['graph'] = None
-                return out, loss, grad
-        self._replay(st)
+        keep = True
+        if act is REPLAY_TIMED:
+            _, _, graph_ms = self._timed(lambda: self._replay(st))
+            keep = pol.replay_timed(graph_ms)
+        else:
+            self._replay(st)
+            pol.replay_done()
         self.arena.bump_version()      # what optimizer.step() does on the host: master weights moved
         self.training_steps += 1
-        return st['out'], st['loss'], st['grad']
+        out, loss, grad = st['out'], st['loss'], st['grad']
+        if not keep:
+            logging.debug('replayed step %.2f ms vs eager %.2f ms -> eager launches from now on', graph_ms, pol.eager_ms)
+            out, loss, grad = out.clone(), loss.clone(), (grad.clone() if grad is not None else None)
+            rec['graph'] = None
+        return out, loss, grad
 
-    def _eager_verdict_withdrawn(self, key):
-        """The eager step of this configuration has been running slower than a replayed graph would for a window of
-        steps (EagerWatch): the host has become the limit after the verdict was taken (a loaded host, a slow box: the
-        eager step needs ~11 ms of host time per ResNet-50 step, a replay none).  The next step captures; the usual
-        check of the second replay against the eager time - now the recent one, loader wait excluded - still applies."""
-        w = self._watch.pop(key)
-        self._graph_eager_for.discard(key)
-        gs = self._gstates.get(key)
-        if gs is None:
-            gs = self._gstates[key] = {'seen': {'n': 4}, 'graph': None}
-        gs['seen'].update(use=True, withdrawn=True, eager_ms=w.recent_ms(), n=max(gs['seen'].get('n', 0), 4))
-        gs['seen'].pop('graph_ms', None)
-        gs['seen'].pop('replays', None)
-        logging.info('eager step %.2f ms against %.2f ms when it was chosen: trying a HIP graph', w.recent_ms(), w.ref_ms)
+    def _capture_for(self, rec, inputs, target, chunk_batch, key):
+        """Capture the step as the policy asked (a refused plan may be followed by a HIP graph in the same step).
+        False: no capture - the policy settled on eager launches, which serve this step too."""
+        pol = rec['policy']
+        plan = pol.next_action() is CAPTURE_PLAN
+        try:
+            try:
+                rec['graph'] = self._capture(inputs, target, chunk_batch, key, plan=plan)
+            except PlanRefused as e:
+                logging.warning('launch plan refused (%s): %s', e, 'HIP graph / eager launches instead')
+                pol.plan_refused()
+                if pol.next_action() is not CAPTURE_GRAPH:
+                    return False
+                plan = False
+                rec['graph'] = self._capture(inputs, target, chunk_batch, key, plan=False)
+        except RuntimeError as e:      # (torch.cuda.OutOfMemoryError is one)
+            if not pol.capture_failed():
+                raise
+            logging.warning('capture of the training step failed (%s): staying with eager launches',
+                            str(e).split('\n')[0][:200])
+            torch.cuda.empty_cache()
+            return False
+        pol.captured_as('plan' if plan else 'graph')
+        return True
+
+    def _timed(self, fn):
+        """fn() between two timing events on a drained device -> (its result, host ms to issue it, device ms)."""
+        torch.cuda.synchronize(self.device)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        res = fn()
+        e1.record()
+        host_ms = (time.perf_counter() - t0) * 1e3
+        e1.synchronize()
+        return res, host_ms, e0.elapsed_time(e1)
+
+    def _watched_eager_step(self, rec, inputs, target, chunk_batch):
+        """The eager step of a configuration whose eager verdict is re-examined while it is in force (EagerWatch).  When
+        the watch fires, the step has been running slower than a replay would for a window of steps: the host has become
+        the limit after the verdict was taken (a loaded host, a slow box: the eager step needs ~11 ms of host time per
+        ResNet-50 step, a replay none), and the policy has the next step capture."""
+        if rec['watch'] is None:
+            rec['watch'] = EagerWatch(rec['policy'].eager_ms)
+        res = self._body(inputs, target, True, chunk_batch)
+        if rec['watch'].step(torch.cuda.current_stream(self.device), self._data_wait_ms):
+            w, rec['watch'] = rec['watch'], None
+            self._make_room()
+            rec['policy'].watch_fired(w.recent_ms())
+            logging.info('eager step %.2f ms against %.2f ms when it was chosen: trying a HIP graph', w.recent_ms(), w.ref_ms)
+        return res
 
     def _feed(self, st, inputs, target):
         """The batch of this step -> where the captured step reads it.  A HIP graph reads static buffers (two copies per
@@ -611,22 +576,7 @@ class Trainer(object):
         except BaseException:
             if rec is not None:
                 rec.destroy()
-            # an aborted step body leaves per-step mailboxes half filled: empty them, the next (eager) step starts clean
-            for m in self._model.modules():
-                h = getattr(m, '_holder', None)
-                if h is not None:
-                    h.dres, h.fused, h.sub = None, False, 1
-                m.__dict__.pop('_lazy_z', None)
-                m.__dict__.pop('_lazy_a', None)
-                if hasattr(m, '_lazy_dy'):
-                    m._lazy_dy = None
-            ops.SIDE._held.clear()
-            ops.SIDE._held_bytes, ops.SIDE.used, ops.SIDE._mark = 0, False, None
-            try:
-                from . import quant as _q
-                _q._MM_STASH.clear()
-            except Exception:
-                pass
+            ops.reset_step_state(self._model)     # per-step mailboxes of the aborted body
             raise
         finally:
             ops.SIDE.capturing = False

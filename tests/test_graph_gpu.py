@@ -136,12 +136,12 @@ def run(mode):
             (key,) = list(tr._gstates.keys())      # the one configuration this loop runs (shapes + step options)
             # Whatever auto decided for this small (host-bound) model: install the state a DEVICE-bound configuration
             # is in after its fourth step - eager verdict, watch armed - with a reference time no real step can meet.
-            tr._gstates[key] = {'seen': {'n': 4, 'use': False, 'eager_ms': 1e-3}, 'graph': None}
-            tr._graph_eager_for.add(key)
-            tr._watch[key] = ca.trainer.EagerWatch(1e-3)
+            tr._gstates[key] = {'policy': ca.step_policy.StepPolicy.eager_verdict(1e-3, mode='auto', plan=tr._plan),
+                                'graph': None, 'watch': ca.trainer.EagerWatch(1e-3)}
         recs.append(tr.train([b])['loss'])
-        states.append((key in tr._graph_eager_for, key in tr._watch,
-                       tr._gstates.get(key, {}).get('graph') is not None))
+        rec = tr._gstates.get(key)
+        states.append((rec is not None and rec['policy'].eager, rec is not None and rec['watch'] is not None,
+                       rec is not None and rec['graph'] is not None))
     torch.cuda.synchronize()
     return recs, states, tr
 
@@ -187,10 +187,9 @@ for b in (big[0], small[0]):
     tr.train([b])
     (k,) = [k for k in tr._gstates if k not in keys]
     keys.append(k)
-    tr._gstates[k] = {'seen': {'n': 4, 'use': False, 'eager_ms': 1e9}, 'graph': None}
-    tr._graph_eager_for.add(k)
-    tr._watch[k] = ca.trainer.EagerWatch(1e9)
-wa, wb = tr._watch[keys[0]], tr._watch[keys[1]]
+    tr._gstates[k] = {'policy': ca.step_policy.StepPolicy.eager_verdict(1e9, mode='auto', plan=tr._plan),
+                      'graph': None, 'watch': ca.trainer.EagerWatch(1e9)}
+wa, wb = tr._gstates[keys[0]]['watch'], tr._gstates[keys[1]]['watch']
 # strictly alternating configurations: every period lies between marks of DIFFERENT watches -> nobody collects one
 for i in range(12):
     tr.train([big[i %% 4] if i %% 2 == 0 else small[i %% 4]])
@@ -253,7 +252,8 @@ def run(break_capture):
 ok, tr_ok = run(False)
 assert any(g['graph'] is not None and g['graph'].get('plan') is not None for g in tr_ok._gstates.values())
 bad, tr_bad = run(True)
-assert all(g['graph'] is None for g in tr_bad._gstates.values()) and len(tr_bad._graph_eager_for) == 1
+assert all(g['graph'] is None for g in tr_bad._gstates.values())
+assert [g['policy'].eager for g in tr_bad._gstates.values()] == [True]
 assert ok == bad, (ok, bad)          # the job went on with eager launches: the same numbers
 print('FALLBACK_OK')
 '''
