@@ -201,3 +201,97 @@ def check_syncbn_against_oracle(outs):
     for k in ('conv1.weight', 'layer2.0.downsample.0.weight', 'fc.weight', 'layer4.1.bn2.bias',
               'bn1.running_mean', 'layer3.0.bn1.running_var', 'layer1.1.bn2.weight'):
         assert rel_l2(outs[0]['sd'][k], ref_sd[k]) < 1e-4, k
+
+
+# ---- exact-arithmetic helpers (tests/test_exact.py and the per-element bounds beside the rel-L2 checks).
+# With small-integer data every product and every partial sum of a convolution is an integer below 2^24, so an fp32
+# accumulation is exact in ANY summation order, tile shape or split count, and the correct result is one fixed bit
+# pattern: the integer itself in fp32, its round-to-nearest-even in bf16 / fp16.
+U_OUT = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11, torch.float32: 2.0 ** -24}
+
+
+def int_tensor(shape, gen, lo=-3, hi=3, density=0.5):
+    """Seeded integer-valued fp64 tensor with values in [lo, hi]; a share `density` of the elements is non-zero."""
+    assert lo <= hi and (lo != 0 or hi != 0)
+    v = torch.randint(lo, hi + 1, tuple(shape), generator=gen)
+    while True:                                   # redraw the zeros: the density is decided by the mask alone
+        z = v == 0
+        if not bool(z.any()):
+            break
+        v = torch.where(z, torch.randint(lo, hi + 1, tuple(shape), generator=gen), v)
+    keep = torch.rand(tuple(shape), generator=gen) < density
+    return torch.where(keep, v, torch.zeros_like(v)).double()
+
+
+def assert_exact_domain(abs_result, n_bits=24):
+    """abs_result: the operation under test evaluated in fp64 on |inputs| (the magnitude sum A of every output
+    element).  A < 2^n_bits bounds every partial sum of every summation order, so no fp32 addition can round."""
+    a = float(abs_result.double().abs().max())
+    assert a < 2.0 ** n_bits, 'left the exact-integer domain: max magnitude sum %g >= 2^%d' % (a, n_bits)
+    return a
+
+
+def assert_not_degenerate(ref):
+    """A reference that is mostly zero, or holds a handful of values, would let a wrong kernel pass."""
+    r = ref.double().flatten()
+    nz = int((r != 0).sum())
+    assert 2 * nz >= r.numel(), 'degenerate reference: only %d of %d elements are non-zero' % (nz, r.numel())
+    sample = r if r.numel() <= (1 << 22) else r[:: r.numel() // (1 << 22)]
+    nd = int(torch.unique(sample).numel())
+    assert nd >= 16, 'degenerate reference: only %d distinct values' % nd
+
+
+def _mismatch_report(bad, out, want, what):
+    """Count, first indices with got / want, and histograms by leading index (image), border / interior pixel (4-D
+    n, h, w, c tensors) and 8-channel chunk of the last dimension."""
+    idx = bad.nonzero()
+    n = idx.shape[0]
+    lines = ['%s: %d of %d elements differ' % (what, n, bad.numel())]
+    names = 'nhwc' if bad.dim() == 4 else ''.join('d%d,' % i for i in range(bad.dim())).rstrip(',')
+    for row in idx[:6].tolist():
+        lines.append('  (%s) = %s: got %r want %r' % (','.join(names) if bad.dim() == 4 else names, tuple(row),
+                                                    float(out[tuple(row)]), float(want[tuple(row)])))
+    lead = torch.bincount(idx[:, 0], minlength=bad.shape[0])
+    top = [(int(i), int(lead[i])) for i in lead.argsort(descending=True)[:8].tolist() if int(lead[i])]
+    lines.append('  by leading index (image / filter): %d of %d touched, largest %s' % (int((lead > 0).sum()),
+                                                                                      bad.shape[0], top))
+    if bad.dim() == 4:
+        H, W = bad.shape[1], bad.shape[2]
+        h, w = idx[:, 1], idx[:, 2]
+        border = (h == 0) | (h == H - 1) | (w == 0) | (w == W - 1)
+        lines.append('  by pixel: %d on the border, %d interior; rows %s cols %s' % (
+            int(border.sum()), int((~border).sum()), sorted(set(h.tolist()))[:12], sorted(set(w.tolist()))[:12]))
+    chunk = torch.bincount(idx[:, -1] // 8, minlength=(bad.shape[-1] + 7) // 8)
+    lines.append('  by 8-channel chunk of the last dimension: %s' % chunk.tolist()[:64])
+    return '\n'.join(lines)
+
+
+def assert_same_values(out, ref_exact, dtype, what):
+    """out == ref_exact.to(dtype) by VALUE on every element (-0.0 == 0.0), and no NaN anywhere in out."""
+    out = out.detach().cpu()
+    assert out.dtype == dtype, (what, out.dtype, dtype)
+    want = ref_exact.detach().cpu().to(dtype)
+    assert tuple(out.shape) == tuple(want.shape), (what, tuple(out.shape), tuple(want.shape))
+    assert not bool(torch.isnan(out).any()), '%s: NaN in the output' % what
+    if torch.equal(out, want):
+        return
+    bad = out != want
+    raise AssertionError(_mismatch_report(bad, out, want, what))
+
+
+def assert_within_forward_bound(out, ref64, A, n, out_dtype, what=''):
+    """Per element: |out - ref| <= u_out*|ref| + 2*n*2^-24*A.  ref64: the fp64 reference, A: the fp64 magnitude sum
+    (the same operation on |inputs|), n: the reduction length.  The textbook forward error bound of an fp32 dot
+    product in any order (gamma_n <= n*u; the factor 2 covers an internal adder that does not round to nearest) plus one
+    rounding to the output format.  Returns the largest |err| / bound."""
+    out = out.detach().cpu().double()
+    ref64, A = ref64.detach().cpu().double(), A.detach().cpu().double()
+    assert tuple(out.shape) == tuple(ref64.shape) == tuple(A.shape), (what, out.shape, ref64.shape, A.shape)
+    assert not bool(torch.isnan(out).any()), '%s: NaN in the output' % what
+    bound = U_OUT[out_dtype] * ref64.abs() + 2.0 * n * 2.0 ** -24 * A
+    err = (out - ref64).abs()
+    bad = err > bound
+    if bool(bad.any()):
+        raise AssertionError(_mismatch_report(bad, out, ref64, '%s: per-element forward bound (n=%d)' % (what, n)))
+    ratio = err / bound.clamp_min(1e-300)
+    return float(ratio.max())

@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import HAS_GPU
-from helpers import rel_l2
+from helpers import assert_within_forward_bound, rel_l2
 
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 
@@ -58,6 +58,19 @@ def _run(N, H, W, C, K, g, st, dtype, dev, beta_check=False):
     ops.gconv2d_wgrad(xh, dyh, dw, K, g, st, beta=0.0)
     dw_k = dw.cpu().view(K, 3, 3, C // g).permute(0, 3, 1, 2)
     assert rel_l2(dw_k, dw_ref) < _tol(dtype, True), ('wgrad', N, H, W, C, K, g, st, dtype)
+    # beside the norms: every element within the forward error bound of an fp32 dot product plus one output rounding,
+    # against the fp64 reference and its magnitude sums (the same operation on the absolute values)
+    xa, wa, da = [t.double().cpu().permute(0, 3, 1, 2).abs() for t in (xh, wh, dyh)]
+    what = str((N, H, W, C, K, g, st, dtype))
+    ratios = (assert_within_forward_bound(y.cpu().permute(0, 3, 1, 2), y_ref, F.conv2d(xa, wa, stride=st, padding=1, groups=g),
+                                          9 * (C // g), dtype, 'gconv fwd ' + what),
+              assert_within_forward_bound(dx.cpu().permute(0, 3, 1, 2), dx_ref,
+                                          torch.nn.grad.conv2d_input(xa.shape, wa, da, stride=st, padding=1, groups=g),
+                                          9 * (K // g), dtype, 'gconv dgrad ' + what),
+              assert_within_forward_bound(dw_k, dw_ref,
+                                          torch.nn.grad.conv2d_weight(xa, wa.shape, da, stride=st, padding=1, groups=g),
+                                          dyh.numel() // K, torch.float32, 'gconv wgrad ' + what))
+    print('gconv max |err| / bound (fwd, dgrad, wgrad) %s: %.3g %.3g %.3g' % ((what,) + ratios))
     if beta_check:
         dw2 = dw.clone()
         ops.gconv2d_wgrad(xh, dyh, dw2, K, g, st, beta=1.0, scale=0.5)

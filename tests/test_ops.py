@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import HAS_GPU
-from helpers import rel_l2
+from helpers import assert_within_forward_bound, rel_l2
 
 MODES = [pytest.param('emul'), pytest.param('gpu', marks=pytest.mark.gpu)]
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
@@ -94,6 +94,20 @@ def _conv_case(cfg, dtype, dev, seed=0):
     dx = ops.conv2d_dgrad(dyh, wc, xh.shape, K, R, R, (st, st), (pad, pad))
     dw = torch.zeros(K, R, R, C, dtype=torch.float32, device=dev)
     ops.conv2d_wgrad(xh, dyh, dw, C, K, R, R, (st, st), (pad, pad), beta=0.0)
+    # beside the norms: every element within the forward error bound of an fp32 dot product plus one output rounding
+    # (helpers.assert_within_forward_bound), against the fp64 reference and its magnitude sums
+    xd, wd, dyd = x.detach().double(), w.detach().double(), dy.double()
+    P, Q = y_ref.shape[2], y_ref.shape[3]
+    conv_x = lambda d, v: torch.nn.grad.conv2d_input(xd.shape, v, d, stride=st, padding=pad)
+    conv_w = lambda a, d: torch.nn.grad.conv2d_weight(a, wd.shape, d, stride=st, padding=pad)
+    ratios = (assert_within_forward_bound(y.cpu().permute(0, 3, 1, 2), F.conv2d(xd, wd, stride=st, padding=pad),
+                                          F.conv2d(xd.abs(), wd.abs(), stride=st, padding=pad), C * R * R, dtype,
+                                          'fwd %s %s' % (cfg, dtype)),
+              assert_within_forward_bound(dx.cpu().permute(0, 3, 1, 2), conv_x(dyd, wd), conv_x(dyd.abs(), wd.abs()),
+                                          K * R * R, dtype, 'dgrad %s %s' % (cfg, dtype)),
+              assert_within_forward_bound(dw.cpu().permute(0, 3, 1, 2), conv_w(xd, dyd), conv_w(xd.abs(), dyd.abs()),
+                                          N * P * Q, torch.float32, 'wgrad %s %s' % (cfg, dtype)))
+    print('max |err| / bound (fwd, dgrad, wgrad) %s %s: %.3g %.3g %.3g' % ((cfg, dtype) + ratios))
     return (rel_l2(y.float().cpu().permute(0, 3, 1, 2), y_ref.detach()),
             rel_l2(dx.float().cpu().permute(0, 3, 1, 2), x.grad),
             rel_l2(dw.cpu().permute(0, 3, 1, 2), w.grad))
