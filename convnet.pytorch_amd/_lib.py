@@ -2,7 +2,8 @@
 
 This is the drop-in boundary: everything above it is Python host code mirroring the reference's
 operator / trainer interface, everything below it is hand-written HIP for gfx950.  The library is
-built in-tree by ``__graft_entry__.build()`` (or ``csrc/build.sh``).
+built in-tree by ``__graft_entry__.build()`` (or ``csrc/build.sh``).  The signatures are not written
+down here: they are parsed from the header the library itself is compiled against (``parse_header``).
 
 There is deliberately NO fallback: if the HIP library is missing, loading raises.  The only other
 library this module can bind is the TEST-ONLY SIMT emulator build of the *same kernel sources*
@@ -11,6 +12,7 @@ suite does that); it is refused whenever a GPU is visible.
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -21,157 +23,52 @@ EMUL_LIB = os.path.join(_HERE, 'libconvnet_emul.so')
 
 F32, BF16, F16 = 0, 1, 2
 
-c_p = ctypes.c_void_p
-c_i = ctypes.c_int
-c_f = ctypes.c_float
-c_ll = ctypes.c_longlong
-c_sz = ctypes.c_size_t
-c_ull = ctypes.c_ulonglong
+HEADER = os.path.join(_HERE, '..', 'include', 'convnet_hip.h')
 
-# name -> (restype, argtypes); mirrors include/convnet_hip.h one to one
-_SIGNATURES = {
-    'cn_last_error': (ctypes.c_char_p, []),
-    'cn_build_info': (ctypes.c_char_p, []),
-    'cn_last_kernel_name': (ctypes.c_char_p, []),
-    'cn_kernel_log': (ctypes.c_char_p, [c_i]),
-    'cn_is_emulator': (c_i, []),
-    'cn_set_option': (c_i, [ctypes.c_char_p, c_i]),
-    'cn_stream_fork': (c_i, [c_p, c_p]),
-    'cn_stream_arm': (c_i, []),
-    'cn_step_timer_mark': (c_i, [c_p, ctypes.c_longlong]),
-    'cn_step_timer_poll': (c_i, [c_p, c_p, c_p]),
-    'cn_stream_disarm': (c_i, []),
-    'cn_plan_begin': (c_i, [c_p, c_p]),
-    'cn_plan_end': (c_i, [c_p]),
-    'cn_plan_import_graph': (c_i, [c_p, c_p]),
-    'cn_plan_replay': (c_i, [c_p]),
-    'cn_plan_info': (c_i, [c_p, c_p]),
-    'cn_plan_bind_input': (c_i, [c_p, c_i, c_p, c_sz]),
-    'cn_plan_set_input': (c_i, [c_p, c_i, c_p]),
-    'cn_plan_describe': (ctypes.c_char_p, [c_p]),
-    'cn_plan_destroy': (c_i, [c_p]),
-    'cn_stream_wait_mark': (c_i, [c_i, c_p]),
-    'cn_conv2d_fwd': (c_i, [c_p, c_p, c_p, c_p] + [c_i] * 11 + [c_i, c_i, c_i, c_p]),
-    'cn_conv2d_bnstats_rows': (c_i, [c_ll]),
-    'cn_conv2d_fwd_bnstats': (c_i, [c_p, c_p, c_p, c_p] + [c_i] * 11 + [c_i, c_i, c_p, c_i, c_p]),
-    'cn_conv2d_fwd_bnstats_centered': (c_i, [c_p, c_p, c_p, c_p] + [c_i] * 11 + [c_i, c_i, c_p, c_i, c_p, c_p]),
-    'cn_conv2d_dgrad': (c_i, [c_p, c_p, c_p, c_p] + [c_i] * 11 + [c_i, c_i, c_p]),
-    'cn_conv2d_dgrad_junction_ok': (c_i, [c_i, c_i, c_i]),
-    'cn_conv2d_dgrad_junction_rows': (c_i, [c_i] * 4),
-    'cn_conv2d_dgrad_junction': (c_i, [c_p, c_p, c_p, c_p, c_i] + [c_i] * 6 + [c_p, c_p, c_p, c_p, c_i, c_p]),
-    'cn_conv2d_dgrad_bnbwd_rows': (c_i, [c_i] * 6),
-    'cn_conv2d_dgrad_bnbwd': (c_i, [c_p, c_p, c_p, c_p] + [c_i] * 11 + [c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_p]),
-    'cn_conv2d_dgrad_sa': (c_i, [c_p, c_p, c_p, c_p, c_i] + [c_i] * 11 + [c_i, c_i, c_p]),
-    'cn_conv2d_dgrad_bnbwd_sa': (c_i, [c_p, c_p, c_p, c_p, c_i] + [c_i] * 11 + [c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_p]),
-    'cn_conv2d_wgrad_workspace': (c_sz, [c_i] * 12),
-    'cn_conv2d_wgrad': (c_i, [c_p, c_p, c_p, c_i] + [c_i] * 11 + [c_i, c_f, c_f, c_p, c_sz, c_p]),
-    'cn_conv2d_fwd_lazyz': (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p] + [c_i] * 6 + [c_p, c_i, c_p, c_p]),
-    'cn_conv2d_dgrad_lazy': (c_i, [c_p, c_p, c_p, c_p, c_p] + [c_i] * 11 + [c_i, c_p]),
-    'cn_conv2d_wgrad_lazy': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i] + [c_i] * 11 + [c_i, c_f, c_f, c_p, c_sz, c_p]),
-    'cn_conv2d_bwd1x1_lazy_ok': (c_i, [c_i, c_i, c_i]),
-    'cn_conv2d_bwd1x1_lazy_workspace': (c_sz, [c_i] * 5),
-    'cn_conv2d_bwd1x1_lazy': (c_i, [c_p] * 7 + [c_i] * 6 + [c_f, c_f, c_p, c_sz, c_p]),
-    'cn_stem_fwd_ok': (c_i, [c_i] * 5),
-    'cn_stem_fwd_rows': (c_i, [c_i, c_i]),
-    'cn_stem_fwd': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
-    'cn_stem_wgrad_ok': (c_i, [c_i] * 5),
-    'cn_stem_wgrad_workspace': (c_sz, [c_i, c_i]),
-    'cn_stem_wgrad': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_p, c_sz, c_p]),
-    'cn_conv3x3_c64_ok': (c_i, [c_i] * 5),
-    'cn_conv3x3_c64_rows': (c_i, [c_i, c_i]),
-    'cn_gconv2d_ok': (c_i, [c_i] * 10),
-    'cn_gconv2d_fwd': (c_i, [c_p, c_p, c_p] + [c_i] * 8 + [c_p]),
-    'cn_gconv2d_dgrad': (c_i, [c_p, c_p, c_p] + [c_i] * 8 + [c_p]),
-    'cn_gconv2d_wgrad_workspace': (c_sz, [c_i] * 8),
-    'cn_gconv2d_wgrad': (c_i, [c_p, c_p, c_p] + [c_i] * 8 + [c_f, c_f, c_p, c_sz, c_p]),
-    'cn_conv3x3_c64': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
-    'cn_conv1x1_stream_fwd_ok': (c_i, [c_i, c_i, c_i]),
-    'cn_conv1x1_stream_fwd_rows': (c_i, [c_i] * 4),
-    'cn_conv1x1_stream_fwd': (c_i, [c_p, c_p, c_p] + [c_i] * 6 + [c_p, c_i, c_p]),
-    'cn_conv2d_dgrad_lazy_stream_ok': (c_i, [c_i, c_i, c_i]),
-    'cn_conv2d_dgrad_lazy_stream': (c_i, [c_p] * 5 + [c_i] * 6 + [c_p]),
-    'cn_conv1x1_stream_fwd_lazya': (c_i, [c_p, c_p, c_i, c_p, c_p, c_p] + [c_i] * 6 + [c_p, c_i, c_p]),
-    'cn_conv3x3_c64_lazya': (c_i, [c_p, c_p, c_i, c_p, c_p, c_p] + [c_i] * 4 + [c_p, c_i, c_p]),
-    'cn_conv2d_dgrad_junction_rows_k': (c_i, [c_i] * 5),
-    'cn_bn_workspace': (c_sz, [c_i, c_i, c_i]),
-    'cn_bn_fwd_train': (c_i, [c_p] * 9 + [c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
-    'cn_bn_fwd_train_partials': (c_i, [c_p] * 9 + [c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_sz, c_p]),
-    'cn_bn_fwd_train_partials_centered': (c_i, [c_p] * 9 + [c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_sz, c_p]),
-    'cn_bn_fwd_infer': (c_i, [c_p] * 7 + [c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
-    'cn_bn_apply_dual': (c_i, [c_p] * 6 + [c_i, c_i, c_i, c_i, c_p]),
-    'cn_bn_bwd': (c_i, [c_p] * 9 + [c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
-    'cn_bn_bwd_partials': (c_i, [c_p] * 7 + [c_f, c_f, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_sz, c_p]),
-    'cn_bn_local_sums': (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
-    'cn_bn_fwd_train_sums': (c_i, [c_p] * 9 + [c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_p, c_ll, c_p]),
-    'cn_bn_bwd_local_sums': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
-    'cn_bn_bwd_sums': (c_i, [c_p] * 9 + [c_f, c_f, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_ll, c_p]),
-    'cn_maxpool_fwd': (c_i, [c_p, c_p, c_p] + [c_i] * 8 + [c_p]),
-    'cn_maxpool_bwd': (c_i, [c_p, c_p, c_p] + [c_i] * 8 + [c_p]),
-    'cn_maxpool_fwd_bnrelu': (c_i, [c_p, c_p, c_p, c_p, c_p] + [c_i] * 8 + [c_p]),
-    'cn_bn_bwd_maxpool': (c_i, [c_p] * 8 + [c_f, c_f, c_p] + [c_i] * 8 + [c_p, c_sz, c_p]),
-    'cn_maxpool_fwd_bnrelu_xmax': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p] + [c_i] * 8 + [c_p]),
-    'cn_bn_bwd_maxpool_xmax': (c_i, [c_p] * 9 + [c_f, c_f, c_p] + [c_i] * 8 + [c_p, c_sz, c_p]),
-    'cn_avgpool_fwd': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
-    'cn_avgpool_bwd': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
-    'cn_nchw_to_nhwc': (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),
-    'cn_u8_nhwc_to_nchw_lut': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
-    'cn_resize_u8_crops': (c_i, [c_p] * 7 + [c_i] * 4 + [c_p]),
-    'cn_nchw_to_pairs': (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),
-    'cn_weight_prep_pairs': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
-    'cn_wgrad_unpack_pairs': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
-    'cn_nhwc_to_nchw': (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),
-    'cn_eltwise': (c_i, [c_i, c_p, c_p, c_p, c_ll, c_i, c_p]),
-    'cn_softmax_ce': (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_f, c_p, c_f, c_p]),
-    'cn_sgd_momentum': (c_i, [c_p, c_p, c_p, c_ll, c_f, c_f, c_f, c_f, c_p, c_p, c_p]),
-    'cn_grad_norm_workspace': (c_sz, []),
-    'cn_grad_norm_clip': (c_i, [c_p, c_ll, c_f, c_f, c_p, c_p, c_f, c_p, c_p]),
-    'cn_weight_prep': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    'cn_weight_prep_multi': (c_i, [c_p, c_p, c_p, c_i, c_ll, c_i, c_p]),
-    'cn_weight_prep_tiled': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
-    'cn_colsum_workspace': (c_sz, [c_i]),
-    'cn_colsum': (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p]),
-    'cn_small_linear': (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
-    'cn_cast_from_f32': (c_i, [c_p, c_p, c_ll, c_i, c_p]),
-    'cn_fill_f32': (c_i, [c_p, c_ll, c_f, c_p]),
-    'cn_minmax_workspace': (c_sz, [c_i, c_ll]),
-    'cn_minmax_rows': (c_i, [c_p, c_i, c_ll, c_i, c_p, c_p, c_sz, c_p]),
-    'cn_qparams': (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_f, c_p]),
-    'cn_quantize': (c_i, [c_p, c_p, c_ll, c_i, c_p, c_p, c_i, c_p, c_i, c_ull, c_p]),
-    'cn_quantize_s': (c_i, [c_p, c_p, c_ll, c_i, c_p, c_p, c_i, c_p, c_i, c_ull, c_p, c_p]),
-    'cn_counter_inc': (c_i, [c_p, c_p]),
-    'cn_quantize_levels': (c_i, [c_p, c_p, c_ll, c_i, c_p, c_p, c_i, c_p, c_i, c_ull, c_p, c_p]),
-    'cn_rangebn_fwd_q8': (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i,
-                                c_p, c_p, c_sz, c_p]),
-    'cn_rangebn_bwd_q8': (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_i, c_p, c_p,
-                                c_p, c_sz, c_p]),
-    'cn_quantize_rows': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p]),
-    'cn_quantize_rows_multi': (c_i, [c_p, c_p, c_p, c_i, c_p]),
-    'cn_rangebn_workspace': (c_sz, [c_i, c_i, c_i]),
-    'cn_rangebn_fwd': (c_i, [c_p] * 7 + [c_f, c_f, c_i, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
-    'cn_rangebn_fwd_q': (c_i, [c_p, c_p, c_i] + [c_p] * 7 + [c_f, c_f, c_i, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_sz, c_p]),
-    'cn_rangebn_bwd_mm': (c_i, [c_p] * 8 + [c_i, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_sz, c_p]),
-    'cn_eltwise_mm_workspace': (c_sz, [c_ll, c_i, c_i]),
-    'cn_eltwise_mm': (c_i, [c_i, c_p, c_p, c_p, c_ll, c_i, c_i, c_p, c_p, c_sz, c_p]),
-    'cn_eltwise_mm_qp': (c_i, [c_i, c_p, c_p, c_p, c_ll, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    'cn_rangebn_bwd': (c_i, [c_p] * 8 + [c_i, c_i, c_i, c_f, c_i, c_p, c_sz, c_p]),
-    'cn_i8_prepare_activation': (c_i, [c_p] * 5 + [c_i] * 11 + [c_p, c_p, c_p, c_p, c_i, c_p]),
-    'cn_i8_prepare_weight': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
-    'cn_conv2d_fwd_i8': (c_i, [c_p] * 10 + [c_i, c_p] + [c_i] * 12 + [c_p]),
-    'cn_comm_load': (c_i, []),
-    'cn_comm_unique_id': (c_i, [c_p]),
-    'cn_comm_init': (c_i, [c_p, c_p, c_i, c_i]),
-    'cn_comm_info': (c_i, [c_p, c_p, c_p, c_p]),
-    'cn_comm_allreduce_bucket': (c_i, [c_p, c_p, c_ll, c_p, c_p, c_i]),
-    'cn_comm_join': (c_i, [c_p, c_p]),
-    'cn_comm_allreduce': (c_i, [c_p, c_p, c_ll, c_i, c_p]),
-    'cn_comm_broadcast': (c_i, [c_p, c_p, c_ll, c_i, c_p]),
-    'cn_comm_destroy': (c_i, [c_p]),
-    'cn_probe_mfma_bf16': (c_i, [c_p, c_p, c_p, c_p]),
-    'cn_probe_mfma_f16': (c_i, [c_p, c_p, c_p, c_p]),
-    'cn_probe_mfma_f32': (c_i, [c_p, c_p, c_p, c_p]),
-    'cn_probe_tr16': (c_i, [c_p, c_p, c_p]),
-    'cn_probe_mfma_i8': (c_i, [c_p, c_p, c_p, c_p]),
-}
+
+class ConvNetHipError(RuntimeError):
+    pass
+
+
+# C type -> ctypes, for everything that is not a pointer (any pointer is a void*, except strings: see _ctype)
+_CTYPES = {'int': ctypes.c_int, 'float': ctypes.c_float, 'long long': ctypes.c_longlong, 'size_t': ctypes.c_size_t,
+           'unsigned long long': ctypes.c_ulonglong, 'cn_status': ctypes.c_int}
+_DECL = re.compile(r'([A-Za-z_][A-Za-z0-9_ ]*?[ *]+)(cn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;')
+
+
+def _ctype(ctype, what):
+    ctype = ' '.join(ctype.replace('*', ' * ').split())
+    if ctype == 'const char *':
+        return ctypes.c_char_p
+    if ctype.endswith('*'):
+        return ctypes.c_void_p
+    if ctype not in _CTYPES:
+        raise ConvNetHipError('convnet_hip.h: unknown type %r in %s' % (ctype, what))
+    return _CTYPES[ctype]
+
+
+def parse_header(text):
+    """The C ABI as declared: name -> (restype, argtypes, is_status) for every `ret cn_name(args);` of the header text.
+    Raises on a type outside the ABI's vocabulary and on any `cn_name(` the declaration pattern did not account for."""
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    named = set(re.findall(r'\b(cn_[a-z0-9_]+)\s*\(', text))
+    text = re.sub(r'^\s*(#|typedef\b|extern "C").*$', '', text, flags=re.M)
+    sigs = {}
+    for ret, name, args in _DECL.findall(text):
+        args = [a.strip() for a in args.split(',')]
+        if args == ['void']:
+            args = []
+        # a parameter is `type name`: the type is everything up to the last identifier
+        argtypes = [_ctype(re.sub(r'[A-Za-z_][A-Za-z0-9_]*$', '', a), '%s(%s)' % (name, a)) for a in args]
+        sigs[name] = (_ctype(ret, 'the return of ' + name), argtypes, ret.strip() == 'cn_status')
+    if set(sigs) != named:
+        raise ConvNetHipError('convnet_hip.h: not parsed as declarations: %s' % sorted(named ^ set(sigs)))
+    return sigs
+
+
+# name -> (restype, argtypes, is_status): include/convnet_hip.h is the only place the ABI is written down
+with open(HEADER) as _f:
+    _SIGNATURES = parse_header(_f.read())
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 
@@ -179,16 +76,23 @@ _lib = None
 _emulated = False
 
 
-class ConvNetHipError(RuntimeError):
-    pass
+def _raise_on_status(lib, name):
+    def errcheck(rc, func, args):
+        if rc != 0:
+            msg = lib.cn_last_error()
+            raise ConvNetHipError('%s failed (rc=%d): %s' % (name, rc, msg.decode() if msg else ''))
+        return rc
+    return errcheck
 
 
 def _bind(path):
     lib = ctypes.CDLL(path)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args, is_status) in _SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError = symbol missing: fail loudly
         fn.restype = res
         fn.argtypes = args
+        if is_status:     # "0 or a negative CN_E* code": a failure raises under the entry point's own name
+            fn.errcheck = _raise_on_status(lib, name)
     return lib
 
 
@@ -235,11 +139,10 @@ def source_hash():
     the hash inside cn_build_info() exactly when the loaded binary was built from these files."""
     import glob
     import hashlib
-    import re
     csrc = os.path.join(_HERE, 'csrc')
     srcs = re.search(r'^SRCS="([^"]+)"', open(os.path.join(csrc, 'build.sh')).read(), re.M).group(1).split()
     files = [os.path.join(csrc, f) for f in srcs] + sorted(glob.glob(os.path.join(csrc, '*.h'))) + \
-        [os.path.join(_HERE, '..', 'include', 'convnet_hip.h')]
+        [HEADER]
     h = hashlib.sha1()
     for f in files:
         with open(f, 'rb') as fh:

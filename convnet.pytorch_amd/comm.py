@@ -19,7 +19,6 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from ._lib import check
 
 _DEFAULT = None     # the communicator of the default data-parallel group (set by Trainer)
 
@@ -72,7 +71,7 @@ class RcclCommunicator(object):
                 rc = L.cn_comm_init(ctypes.byref(self._h), box[0], self.rank, self.world)
             _agree(rc == 0, 'ncclCommInitRank', _lib.last_error() if rc != 0 else None, process_group, self.device)
             ver = ctypes.c_int(0)
-            check(L.cn_comm_info(self._h, None, None, ctypes.byref(ver)), 'cn_comm_info')
+            L.cn_comm_info(self._h, None, None, ctypes.byref(ver))
             self.rccl_version = ver.value
         except Exception:
             # a rank whose own cn_comm_init succeeded still gets here when a PEER failed (the agreement step raises on
@@ -86,24 +85,23 @@ class RcclCommunicator(object):
         what is queued on `streams` (1 or 2 raw hipStream_t)."""
         a = streams[0]
         b = streams[1] if len(streams) > 1 else None
-        check(_lib.load().cn_comm_allreduce_bucket(self._h, view.data_ptr(), view.numel(), a, b, len(streams)),
-              'cn_comm_allreduce_bucket')
+        _lib.load().cn_comm_allreduce_bucket(self._h, view.data_ptr(), view.numel(), a, b, len(streams))
 
     def join(self, stream):
-        check(_lib.load().cn_comm_join(self._h, stream), 'cn_comm_join')
+        _lib.load().cn_comm_join(self._h, stream)
 
     def allreduce_(self, t):
         """In-stream SUM all-reduce of a contiguous fp32 / fp64 tensor on torch's current stream."""
         code = {torch.float32: 0, torch.float64: 2}[t.dtype]
-        check(_lib.load().cn_comm_allreduce(self._h, t.data_ptr(), t.numel(), code,
-                                            torch.cuda.current_stream(t.device).cuda_stream), 'cn_comm_allreduce')
+        _lib.load().cn_comm_allreduce(self._h, t.data_ptr(), t.numel(), code,
+                                      torch.cuda.current_stream(t.device).cuda_stream)
         return t
 
     def broadcast_(self, t, root=0):
         if not t.is_contiguous():
             raise _lib.ConvNetHipError('broadcast_ needs a contiguous tensor')
-        check(_lib.load().cn_comm_broadcast(self._h, t.data_ptr(), t.numel() * t.element_size(), root,
-                                            torch.cuda.current_stream(t.device).cuda_stream), 'cn_comm_broadcast')
+        _lib.load().cn_comm_broadcast(self._h, t.data_ptr(), t.numel() * t.element_size(), root,
+                                      torch.cuda.current_stream(t.device).cuda_stream)
         return t
 
     def destroy(self):

@@ -753,12 +753,12 @@ static int bn_fwd_tail(const float* partial, int nrb, const void* y, const void*
 }
 
 // Training forward.  stats_out = [save_mean | save_invstd | scale | shift] (4*C floats).
-extern "C" int cn_bn_fwd_train(const void* y, const void* residual, void* z, unsigned char* relu_mask,
-                               const float* gamma,
-                               const float* beta, float* running_mean, float* running_var,
-                               long long* num_batches_tracked, float momentum, float eps, float* stats_out,
-                               int M, int C, int relu, int dtype, void* workspace, size_t ws_bytes,
-                               void* stream_) {
+extern "C" cn_status cn_bn_fwd_train(const void* y, const void* residual, void* z, unsigned char* relu_mask,
+                                     const float* gamma,
+                                     const float* beta, float* running_mean, float* running_var,
+                                     long long* num_batches_tracked, float momentum, float eps, float* stats_out,
+                                     int M, int C, int relu, int dtype, void* workspace, size_t ws_bytes,
+                                     void* stream_) {
   int rc = bn_check("bn_fwd_train", M, C, dtype);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)stream_;
@@ -809,12 +809,12 @@ static int bn_fwd_train_partials_impl(const void* y, const void* residual, void*
                      num_batches_tracked, momentum, eps, stats_out, M, C, relu, dtype, m, stream, centered);
 }
 
-extern "C" int cn_bn_fwd_train_partials(const void* y, const void* residual, void* z, unsigned char* relu_mask,
-                                        const float* gamma, const float* beta, float* running_mean,
-                                        float* running_var, long long* num_batches_tracked, float momentum,
-                                        float eps, float* stats_out, int M, int C, int relu, int dtype,
-                                        const float* partial, int nrb, void* workspace, size_t ws_bytes,
-                                        void* stream_) {
+extern "C" cn_status cn_bn_fwd_train_partials(const void* y, const void* residual, void* z, unsigned char* relu_mask,
+                                              const float* gamma, const float* beta, float* running_mean,
+                                              float* running_var, long long* num_batches_tracked, float momentum,
+                                              float eps, float* stats_out, int M, int C, int relu, int dtype,
+                                              const float* partial, int nrb, void* workspace, size_t ws_bytes,
+                                              void* stream_) {
   return bn_fwd_train_partials_impl(y, residual, z, relu_mask, gamma, beta, running_mean, running_var,
                                     num_batches_tracked, momentum, eps, stats_out, M, C, relu, dtype, partial, nrb,
                                     workspace, ws_bytes, stream_, 0);
@@ -822,22 +822,22 @@ extern "C" int cn_bn_fwd_train_partials(const void* y, const void* residual, voi
 
 // Partials that cn_conv2d_fwd_bnstats_centered emitted with pivot = running_mean (as it is now, before this call
 // updates it): sum (y - running_mean) | sum (y - running_mean)^2 per row.
-extern "C" int cn_bn_fwd_train_partials_centered(const void* y, const void* residual, void* z,
-                                                 unsigned char* relu_mask, const float* gamma, const float* beta,
-                                                 float* running_mean, float* running_var,
-                                                 long long* num_batches_tracked, float momentum, float eps,
-                                                 float* stats_out, int M, int C, int relu, int dtype,
-                                                 const float* partial, int nrb, void* workspace, size_t ws_bytes,
-                                                 void* stream_) {
+extern "C" cn_status cn_bn_fwd_train_partials_centered(const void* y, const void* residual, void* z,
+                                                       unsigned char* relu_mask, const float* gamma, const float* beta,
+                                                       float* running_mean, float* running_var,
+                                                       long long* num_batches_tracked, float momentum, float eps,
+                                                       float* stats_out, int M, int C, int relu, int dtype,
+                                                       const float* partial, int nrb, void* workspace, size_t ws_bytes,
+                                                       void* stream_) {
   return bn_fwd_train_partials_impl(y, residual, z, relu_mask, gamma, beta, running_mean, running_var,
                                     num_batches_tracked, momentum, eps, stats_out, M, C, relu, dtype, partial, nrb,
                                     workspace, ws_bytes, stream_, 1);
 }
 
 // Inference forward from running statistics.  coeffs = scratch of 2*C floats.
-extern "C" int cn_bn_fwd_infer(const void* y, const void* residual, void* z, const float* gamma,
-                               const float* beta, const float* running_mean, const float* running_var,
-                               float eps, float* coeffs, int M, int C, int relu, int dtype, void* stream_) {
+extern "C" cn_status cn_bn_fwd_infer(const void* y, const void* residual, void* z, const float* gamma,
+                                     const float* beta, const float* running_mean, const float* running_var,
+                                     float eps, float* coeffs, int M, int C, int relu, int dtype, void* stream_) {
   int rc = bn_check("bn_fwd_infer", M, C, dtype);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)stream_;
@@ -858,9 +858,9 @@ extern "C" int cn_bn_fwd_infer(const void* y, const void* residual, void* z, con
 // stats / res_stats = the 4*C floats [save_mean | save_invstd | scale | shift] of the junction / shortcut BatchNorm.
 // Bit-identical to the shortcut BatchNorm's own apply followed by the junction's (tests/test_ops.py), without the
 // write and the re-read of the normalised shortcut tensor.
-extern "C" int cn_bn_apply_dual(const void* y, const void* res_y, void* z, unsigned char* relu_mask,
-                                const float* stats, const float* res_stats, int M, int C, int relu, int dtype,
-                                void* stream_) {
+extern "C" cn_status cn_bn_apply_dual(const void* y, const void* res_y, void* z, unsigned char* relu_mask,
+                                      const float* stats, const float* res_stats, int M, int C, int relu, int dtype,
+                                      void* stream_) {
   int rc = bn_check("bn_apply_dual", M, C, dtype);
   if (rc) return rc;
   if (y == nullptr || res_y == nullptr || z == nullptr || stats == nullptr || res_stats == nullptr) {
@@ -893,10 +893,10 @@ extern "C" int cn_bn_apply_dual(const void* y, const void* res_y, void* z, unsig
 // Training backward.  stats = the 4*C floats written by cn_bn_fwd_train; coef_scratch = 3*C floats.
 // dgamma/dbeta are written (beta_acc = 0) or accumulated (beta_acc = 1).  dres (optional) receives
 // the masked upstream gradient for the residual branch.
-extern "C" int cn_bn_bwd(const void* dz, const void* y, const unsigned char* relu_mask, const float* gamma,
-                         const float* stats, void* dy, void* dres, float* dgamma, float* dbeta,
-                         float beta_acc, float gscale, float* coef_scratch, int M, int C, int relu, int dtype,
-                         void* workspace, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_bn_bwd(const void* dz, const void* y, const unsigned char* relu_mask, const float* gamma,
+                               const float* stats, void* dy, void* dres, float* dgamma, float* dbeta,
+                               float beta_acc, float gscale, float* coef_scratch, int M, int C, int relu, int dtype,
+                               void* workspace, size_t ws_bytes, void* stream_) {
   int rc = bn_check("bn_bwd", M, C, dtype);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)stream_;
@@ -934,12 +934,12 @@ extern "C" int cn_bn_bwd(const void* dz, const void* y, const unsigned char* rel
 }
 
 // Training backward when the producer of the upstream gradient already masked it and reduced it
-// (cn_conv2d_dgrad_bnbwd): g = dz * relu_mask, partial = [nrb][2*C] floats of sum g | sum g*xhat.
+// (cn_conv2d_dgrad_bnbwd_sa): g = dz * relu_mask, partial = [nrb][2*C] floats of sum g | sum g*xhat.
 // Runs finalize + apply only (no second pass over g and y for the sums, no dres: it is g itself).
-extern "C" int cn_bn_bwd_partials(const void* g, const void* y, const float* gamma, const float* stats, void* dy,
-                                  float* dgamma, float* dbeta, float beta_acc, float gscale,
-                                  float* coef_scratch, int M, int C, int dtype, const float* partial, int nrb,
-                                  void* workspace, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_bn_bwd_partials(const void* g, const void* y, const float* gamma, const float* stats, void* dy,
+                                        float* dgamma, float* dbeta, float beta_acc, float gscale,
+                                        float* coef_scratch, int M, int C, int dtype, const float* partial, int nrb,
+                                        void* workspace, size_t ws_bytes, void* stream_) {
   int rc = bn_check("bn_bwd_partials", M, C, dtype);
   if (rc) return rc;
   if (partial == nullptr || nrb <= 0) { cn_set_error("bn_bwd_partials: no partials"); return CN_EINVAL; }
@@ -1059,8 +1059,8 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_sums_kernel(const double*
 
 // This rank's [sum y | sum y^2] (2*C doubles).  partial/nrb: rows a conv epilogue already produced
 // (cn_conv2d_fwd_bnstats), or NULL/0 to run the statistics pass over y here.
-extern "C" int cn_bn_local_sums(const void* y, int M, int C, int dtype, const float* partial, int nrb, double* sums,
-                                void* workspace, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_bn_local_sums(const void* y, int M, int C, int dtype, const float* partial, int nrb, double* sums,
+                                      void* workspace, size_t ws_bytes, void* stream_) {
   int rc = bn_check("bn_local_sums", M, C, dtype);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)stream_;
@@ -1081,11 +1081,11 @@ extern "C" int cn_bn_local_sums(const void* y, int M, int C, int dtype, const fl
 }
 
 // Training forward from (all-reduced) sums over m_total rows; M = this rank's rows.
-extern "C" int cn_bn_fwd_train_sums(const void* y, const void* residual, void* z, unsigned char* relu_mask,
-                                    const float* gamma, const float* beta, float* running_mean, float* running_var,
-                                    long long* num_batches_tracked, float momentum, float eps, float* stats_out,
-                                    int M, int C, int relu, int dtype, const double* sums, long long m_total,
-                                    void* stream_) {
+extern "C" cn_status cn_bn_fwd_train_sums(const void* y, const void* residual, void* z, unsigned char* relu_mask,
+                                          const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                          long long* num_batches_tracked, float momentum, float eps, float* stats_out,
+                                          int M, int C, int relu, int dtype, const double* sums, long long m_total,
+                                          void* stream_) {
   int rc = bn_check("bn_fwd_train_sums", M, C, dtype);
   if (rc) return rc;
   if (sums == nullptr || m_total < M) { cn_set_error("bn_fwd_train_sums: bad sums / m_total"); return CN_EINVAL; }
@@ -1103,9 +1103,9 @@ extern "C" int cn_bn_fwd_train_sums(const void* y, const void* residual, void* z
 
 // This rank's [sum g | sum g*xhat] (2*C doubles), g = dz * relu_mask.  partial/nrb: rows a dgrad
 // epilogue already produced (then dz is g), or NULL/0 to run the reduction pass here.
-extern "C" int cn_bn_bwd_local_sums(const void* dz, const void* y, const unsigned char* relu_mask,
-                                    const float* stats, int M, int C, int relu, int dtype, const float* partial,
-                                    int nrb, double* sums, void* workspace, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_bn_bwd_local_sums(const void* dz, const void* y, const unsigned char* relu_mask,
+                                          const float* stats, int M, int C, int relu, int dtype, const float* partial,
+                                          int nrb, double* sums, void* workspace, size_t ws_bytes, void* stream_) {
   int rc = bn_check("bn_bwd_local_sums", M, C, dtype);
   if (rc) return rc;
   hipStream_t stream = (hipStream_t)stream_;
@@ -1127,11 +1127,11 @@ extern "C" int cn_bn_bwd_local_sums(const void* dz, const void* y, const unsigne
 
 // Training backward from sums: dgamma/dbeta from `local_sums`, dy from `global_sums` / m_total.
 // pre_masked != 0: dz is already g (masked by the dgrad epilogue).
-extern "C" int cn_bn_bwd_sums(const void* dz, const void* y, const unsigned char* relu_mask, const float* gamma,
-                              const float* stats, void* dy, void* dres, float* dgamma, float* dbeta, float beta_acc,
-                              float gscale, float* coef_scratch, int M, int C, int relu, int pre_masked, int dtype,
-                              const double* local_sums, const double* global_sums, long long m_total,
-                              void* stream_) {
+extern "C" cn_status cn_bn_bwd_sums(const void* dz, const void* y, const unsigned char* relu_mask, const float* gamma,
+                                    const float* stats, void* dy, void* dres, float* dgamma, float* dbeta, float beta_acc,
+                                    float gscale, float* coef_scratch, int M, int C, int relu, int pre_masked, int dtype,
+                                    const double* local_sums, const double* global_sums, long long m_total,
+                                    void* stream_) {
   int rc = bn_check("bn_bwd_sums", M, C, dtype);
   if (rc) return rc;
   if (local_sums == nullptr || global_sums == nullptr || m_total < M) {
@@ -1215,20 +1215,20 @@ static int bn_bwd_maxpool_impl(const void* dpool, const unsigned char* idx, cons
   return cn_check_launch("bn_bwd_maxpool");
 }
 
-extern "C" int cn_bn_bwd_maxpool(const void* dpool, const unsigned char* idx, const void* y, const float* gamma,
-                                 const float* stats, void* dy, float* dgamma, float* dbeta, float beta_acc,
-                                 float gscale, float* coef_scratch, int N, int H, int W, int C, int k, int stride,
-                                 int pad, int dtype, void* workspace, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_bn_bwd_maxpool(const void* dpool, const unsigned char* idx, const void* y, const float* gamma,
+                                       const float* stats, void* dy, float* dgamma, float* dbeta, float beta_acc,
+                                       float gscale, float* coef_scratch, int N, int H, int W, int C, int k, int stride,
+                                       int pad, int dtype, void* workspace, size_t ws_bytes, void* stream_) {
   return bn_bwd_maxpool_impl(dpool, idx, y, nullptr, gamma, stats, dy, dgamma, dbeta, beta_acc, gscale, coef_scratch, N,
                              H, W, C, k, stride, pad, dtype, workspace, ws_bytes, stream_);
 }
 
 // With the winning taps' pre-BatchNorm values (cn_maxpool_fwd_bnrelu_xmax): the reduction reads dpool and xmax only.
-extern "C" int cn_bn_bwd_maxpool_xmax(const void* dpool, const unsigned char* idx, const void* y, const void* xmax,
-                                      const float* gamma, const float* stats, void* dy, float* dgamma, float* dbeta,
-                                      float beta_acc, float gscale, float* coef_scratch, int N, int H, int W, int C,
-                                      int k, int stride, int pad, int dtype, void* workspace, size_t ws_bytes,
-                                      void* stream_) {
+extern "C" cn_status cn_bn_bwd_maxpool_xmax(const void* dpool, const unsigned char* idx, const void* y, const void* xmax,
+                                            const float* gamma, const float* stats, void* dy, float* dgamma, float* dbeta,
+                                            float beta_acc, float gscale, float* coef_scratch, int N, int H, int W, int C,
+                                            int k, int stride, int pad, int dtype, void* workspace, size_t ws_bytes,
+                                            void* stream_) {
   if (xmax == nullptr) { cn_set_error("bn_bwd_maxpool_xmax: no xmax tensor"); return CN_EINVAL; }
   return bn_bwd_maxpool_impl(dpool, idx, y, xmax, gamma, stats, dy, dgamma, dbeta, beta_acc, gscale, coef_scratch, N, H,
                              W, C, k, stride, pad, dtype, workspace, ws_bytes, stream_);

@@ -27,12 +27,12 @@
 // The TEST-ONLY CPU emulator has no devices and no RCCL: the host tests run the data-parallel path over gloo.
 extern "C" int cn_comm_load(void) { cn_set_error("cn_comm: not available in the emulator build"); return CN_ERCCL; }
 extern "C" int cn_comm_unique_id(char*) { cn_set_error("cn_comm: not available in the emulator build"); return CN_ERCCL; }
-extern "C" int cn_comm_init(void**, const char*, int, int) { cn_set_error("cn_comm: not available in the emulator build"); return CN_ERCCL; }
-extern "C" int cn_comm_info(void*, int*, int*, int*) { return CN_ERCCL; }
-extern "C" int cn_comm_allreduce_bucket(void*, float*, long long, void*, void*, int) { return CN_ERCCL; }
-extern "C" int cn_comm_join(void*, void*) { return CN_ERCCL; }
-extern "C" int cn_comm_allreduce(void*, void*, long long, int, void*) { return CN_ERCCL; }
-extern "C" int cn_comm_broadcast(void*, void*, long long, int, void*) { return CN_ERCCL; }
+extern "C" int cn_comm_init(void**, const void*, int, int) { cn_set_error("cn_comm: not available in the emulator build"); return CN_ERCCL; }
+extern "C" cn_status cn_comm_info(void*, int*, int*, int*) { return CN_ERCCL; }
+extern "C" cn_status cn_comm_allreduce_bucket(void*, float*, long long, void*, void*, int) { return CN_ERCCL; }
+extern "C" cn_status cn_comm_join(void*, void*) { return CN_ERCCL; }
+extern "C" cn_status cn_comm_allreduce(void*, void*, long long, int, void*) { return CN_ERCCL; }
+extern "C" cn_status cn_comm_broadcast(void*, void*, long long, int, void*) { return CN_ERCCL; }
 extern "C" int cn_comm_destroy(void*) { return CN_OK; }
 int cn_comm_allreduce_bucket_issue(void*, float*, long long, void*, void*, int) { return CN_ERCCL; }
 int cn_comm_join_issue(void*, void*) { return CN_ERCCL; }
@@ -144,7 +144,7 @@ extern "C" int cn_comm_unique_id(char* id128) {
 }
 
 // Collective over all `world` ranks; binds the communicator to the CURRENT HIP device of the calling thread.
-extern "C" int cn_comm_init(void** handle, const char* id128, int rank, int world) {
+extern "C" int cn_comm_init(void** handle, const void* id128, int rank, int world) {
   const RcclApi* api = rccl();
   if (api == nullptr) return CN_ERCCL;
   if (handle == nullptr || id128 == nullptr || world < 1 || rank < 0 || rank >= world) {
@@ -170,7 +170,7 @@ extern "C" int cn_comm_init(void** handle, const char* id128, int rank, int worl
   return CN_OK;
 }
 
-extern "C" int cn_comm_info(void* handle, int* rank, int* world, int* rccl_version) {
+extern "C" cn_status cn_comm_info(void* handle, int* rank, int* world, int* rccl_version) {
   Comm* c = (Comm*)handle;
   const RcclApi* api = rccl();
   if (c == nullptr || api == nullptr) { cn_set_error("cn_comm_info: no communicator"); return CN_EINVAL; }
@@ -185,13 +185,9 @@ extern "C" int cn_comm_info(void* handle, int* rank, int* world, int* rccl_versi
 // (NULL there means the default stream, as everywhere in this ABI).
 // (cn_comm_allreduce_bucket / _join / _allreduce: while a launch plan is being recorded - plan.hip - the call is
 // logged, not issued: the recording runs under stream capture, RCCL runs live in every replay.)
-void cn_plan_rec_comm(int kind, void* comm, void* buf, long long count, int dtype, void* s0, void* s1, int n_after);
-int cn_comm_allreduce_bucket_issue(void* handle, float* buf, long long count, void* after_a, void* after_b, int n_after);
-int cn_comm_join_issue(void* handle, void* stream);
-int cn_comm_allreduce_issue(void* handle, void* buf, long long count, int dtype, void* stream);
 
-extern "C" int cn_comm_allreduce_bucket(void* handle, float* buf, long long count, void* after_a, void* after_b,
-                                        int n_after) {
+extern "C" cn_status cn_comm_allreduce_bucket(void* handle, float* buf, long long count, void* after_a, void* after_b,
+                                              int n_after) {
   if (cn_plan_recording) {
     if (handle == nullptr || buf == nullptr || count <= 0 || n_after < 0 || n_after > 2) { cn_set_error("cn_comm_allreduce_bucket: bad arguments"); return CN_EINVAL; }
     cn_plan_rec_comm(0, handle, buf, count, 0, after_a, after_b, n_after);
@@ -219,7 +215,7 @@ int cn_comm_allreduce_bucket_issue(void* handle, float* buf, long long count, vo
 }
 
 // `stream` waits for every bucket all-reduce queued so far.
-extern "C" int cn_comm_join(void* handle, void* stream) {
+extern "C" cn_status cn_comm_join(void* handle, void* stream) {
   if (cn_plan_recording) {
     if (handle == nullptr) { cn_set_error("cn_comm_join: no communicator"); return CN_EINVAL; }
     cn_plan_rec_comm(1, handle, nullptr, 0, 0, stream, nullptr, 0);
@@ -237,7 +233,7 @@ int cn_comm_join_issue(void* handle, void* stream) {
 }
 
 // In-stream, in-place SUM all-reduce.  dtype: 0 = fp32, 2 = fp64 (the SyncBatchNorm sums).
-extern "C" int cn_comm_allreduce(void* handle, void* buf, long long count, int dtype, void* stream) {
+extern "C" cn_status cn_comm_allreduce(void* handle, void* buf, long long count, int dtype, void* stream) {
   if (cn_plan_recording) {
     if (handle == nullptr || buf == nullptr || count <= 0 || (dtype != 0 && dtype != 2)) { cn_set_error("cn_comm_allreduce: bad arguments (dtype %d)", dtype); return CN_EINVAL; }
     cn_plan_rec_comm(2, handle, buf, count, dtype, stream, nullptr, 0);
@@ -258,7 +254,7 @@ int cn_comm_allreduce_issue(void* handle, void* buf, long long count, int dtype,
 }
 
 // In-stream broadcast of `nbytes` bytes from rank `root` (parameters at construction, BN buffers before validate).
-extern "C" int cn_comm_broadcast(void* handle, void* buf, long long nbytes, int root, void* stream) {
+extern "C" cn_status cn_comm_broadcast(void* handle, void* buf, long long nbytes, int root, void* stream) {
   Comm* c = (Comm*)handle;
   const RcclApi* api = rccl();
   if (c == nullptr || api == nullptr || buf == nullptr || nbytes <= 0 || root < 0 || root >= c->world) {

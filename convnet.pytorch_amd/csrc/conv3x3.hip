@@ -250,7 +250,7 @@ extern "C" int cn_conv3x3_c64_rows(int N, int H) { return c3_wgs(N * ((H + C3_RO
 // y = conv3x3(x, w), stride 1, pad 1, 64 -> 64 channels, NHWC.  flip = 0: forward with w = KRSC filter [64][3][3][64];
 // flip = 1: data gradient (x = dy, w = the CRSK filter: rows = input channels of the convolution).  partial (optional,
 // forward): cn_conv3x3_c64_rows(N, H) rows of 128 floats [sum | sum of squares] of the stored outputs for
-// cn_bn_fwd_train_partials.  Same output bits as cn_conv2d_fwd / cn_conv2d_dgrad.
+// cn_bn_fwd_train_partials.  Same output bits as cn_conv2d_fwd / cn_conv2d_dgrad_sa.
 static int c3_impl(const char* who, const void* x, const float* xf, int relu, void* a_out, const void* w, void* y, int N,
                    int H, int W, int dtype, int flip, float* partial, int partial_rows, void* stream) {
   if (x == nullptr || w == nullptr || y == nullptr) { cn_set_error("%s: null operand", who); return CN_EINVAL; }
@@ -276,16 +276,16 @@ static int c3_impl(const char* who, const void* x, const float* xf, int relu, vo
   }
   return cn_check_launch("conv3x3_c64");
 }
-extern "C" int cn_conv3x3_c64(const void* x, const void* w, void* y, int N, int H, int W, int dtype, int flip,
-                              float* partial, int partial_rows, void* stream) {
+extern "C" cn_status cn_conv3x3_c64(const void* x, const void* w, void* y, int N, int H, int W, int dtype, int flip,
+                                    float* partial, int partial_rows, void* stream) {
   return c3_impl("conv3x3_c64", x, nullptr, 0, nullptr, w, y, N, H, W, dtype, flip, partial, partial_rows, stream);
 }
 // "Lazy a" (forward): cn_conv3x3_c64 whose input is still the INPUT bn_y of the BatchNorm in front of the convolution
 // (stats = [mean | invstd | scale | shift] of 64 channels): a = relu?(bn_y * scale + shift) is formed on the way into the
 // halo and written to a_out [N][H][W][64] (cn_conv1x1_stream_fwd_lazya's contract for the 3x3 halo kernel; padding stays
 // zero: it pads a, not bn_y).  Same a and y bits as the apply pass followed by cn_conv3x3_c64.
-extern "C" int cn_conv3x3_c64_lazya(const void* bn_y, const float* stats, int relu, void* a_out, const void* w, void* y,
-                                    int N, int H, int W, int dtype, float* partial, int partial_rows, void* stream) {
+extern "C" cn_status cn_conv3x3_c64_lazya(const void* bn_y, const float* stats, int relu, void* a_out, const void* w, void* y,
+                                          int N, int H, int W, int dtype, float* partial, int partial_rows, void* stream) {
   if (stats == nullptr || a_out == nullptr) { cn_set_error("conv3x3_c64_lazya: null operand"); return CN_EINVAL; }
   return c3_impl("conv3x3_c64_lazya", bn_y, stats + 2 * 64, relu, a_out, w, y, N, H, W, dtype, 0, partial, partial_rows, stream);
 }

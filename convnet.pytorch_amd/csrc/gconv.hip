@@ -21,11 +21,6 @@
 #include "cn_api_internal.h"
 #include <type_traits>
 
-extern "C" int cn_gconv2d_ok(int C, int K, int groups, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
-                             int dtype);
-int wg_launch_reduce(hipStream_t stream, const float* part, float* dw, int nsplit, int Co, int ntaps, int Ci, int Creal,
-                     float beta, float scale);
-
 #define GC_MAXRED 64    /* reduction channels per channel block */
 #define GC_WAVES 4
 
@@ -378,8 +373,8 @@ static int gc_run(const char* who, const void* src, const void* w, void* out, in
 }
 
 // y[N][P][Q][K] = grouped conv3x3(x[N][H][W][C], w[K][3][3][C/g]), stride `stride`, padding 1.
-extern "C" int cn_gconv2d_fwd(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int groups,
-                              int stride, int dtype, void* stream) {
+extern "C" cn_status cn_gconv2d_fwd(const void* x, const void* w, void* y, int N, int H, int W, int C, int K, int groups,
+                                    int stride, int dtype, void* stream) {
   if (x == nullptr || w == nullptr || y == nullptr) { cn_set_error("gconv2d_fwd: null operand"); return CN_EINVAL; }
   const int rc = gc_check("gconv2d_fwd", N, H, W, C, K, groups, stride, dtype);
   if (rc != CN_OK) return rc;
@@ -388,8 +383,8 @@ extern "C" int cn_gconv2d_fwd(const void* x, const void* w, void* y, int N, int 
 }
 
 // dx[N][H][W][C] from dy[N][P][Q][K] and the same filter w[K][3][3][C/g].
-extern "C" int cn_gconv2d_dgrad(const void* dy, const void* w, void* dx, int N, int H, int W, int C, int K, int groups,
-                                int stride, int dtype, void* stream) {
+extern "C" cn_status cn_gconv2d_dgrad(const void* dy, const void* w, void* dx, int N, int H, int W, int C, int K, int groups,
+                                      int stride, int dtype, void* stream) {
   if (dy == nullptr || w == nullptr || dx == nullptr) { cn_set_error("gconv2d_dgrad: null operand"); return CN_EINVAL; }
   const int rc = gc_check("gconv2d_dgrad", N, H, W, C, K, groups, stride, dtype);
   if (rc != CN_OK) return rc;
@@ -418,9 +413,9 @@ extern "C" size_t cn_gconv2d_wgrad_workspace(int N, int H, int W, int C, int K, 
 }
 
 // dw[K][3][3][C/g] (fp32) = beta * dw + scale * wgrad(x, dy); `workspace` of cn_gconv2d_wgrad_workspace bytes.
-extern "C" int cn_gconv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int groups,
-                                int stride, int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
-                                void* stream) {
+extern "C" cn_status cn_gconv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int groups,
+                                      int stride, int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
+                                      void* stream) {
   if (x == nullptr || dy == nullptr || dw == nullptr) { cn_set_error("gconv2d_wgrad: null operand"); return CN_EINVAL; }
   const int rc = gc_check("gconv2d_wgrad", N, H, W, C, K, groups, stride, dtype);
   if (rc != CN_OK) return rc;

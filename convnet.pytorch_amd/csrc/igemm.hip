@@ -954,9 +954,6 @@ struct IgLazyZ {   // XF mode 3 operands (see IgemmParams::xf2)
   unsigned char* mask;
 };
 
-int cn_dense_smallm(const void* A, const void* B, void* C, const float* bias, int M, int N, int Kd, int dtype, int out_f32,
-                    int relu, hipStream_t stream);
-
 static int ig_conv_fwd(const void* x, const void* w_krsc, void* y, const float* bias, float* stats, int N, int H,
                        int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
                        int dtype, int out_f32, int relu, void* stream, const float* xf = nullptr, int xf_relu = 0,
@@ -996,9 +993,9 @@ static int ig_conv_fwd(const void* x, const void* w_krsc, void* y, const float* 
   return ig_dispatch(p, dtype, (hipStream_t)stream);
 }
 
-extern "C" int cn_conv2d_fwd(const void* x, const void* w_krsc, void* y, const float* bias, int N, int H,
-                             int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
-                             int pad_w, int dtype, int out_f32, int relu, void* stream) {
+extern "C" cn_status cn_conv2d_fwd(const void* x, const void* w_krsc, void* y, const float* bias, int N, int H,
+                                   int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
+                                   int pad_w, int dtype, int out_f32, int relu, void* stream) {
   return ig_conv_fwd(x, w_krsc, y, bias, nullptr, N, H, W, C, K, R, S, stride_h, stride_w, pad_h, pad_w, dtype,
                      out_f32, relu, stream);
 }
@@ -1010,10 +1007,10 @@ extern "C" int cn_conv2d_bnstats_rows(long long M) { return (int)((M + 127) / 12
 // the outputs it stores: partial[row][0:K] = sum, partial[row][K:2K] = sum of squares, with
 // cn_conv2d_bnstats_rows(N*P*Q) rows.  cn_bn_fwd_train_partials consumes them, which removes the
 // statistics pass over y (one full HBM read of the conv output per BatchNorm).
-extern "C" int cn_conv2d_fwd_bnstats(const void* x, const void* w_krsc, void* y, const float* bias, int N, int H,
-                                     int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
-                                     int pad_w, int dtype, int relu, float* partial, int partial_rows,
-                                     void* stream) {
+extern "C" cn_status cn_conv2d_fwd_bnstats(const void* x, const void* w_krsc, void* y, const float* bias, int N, int H,
+                                           int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
+                                           int pad_w, int dtype, int relu, float* partial, int partial_rows,
+                                           void* stream) {
   const long long P = (H + 2 * pad_h - R) / stride_h + 1, Q = (W + 2 * pad_w - S) / stride_w + 1;
   if (partial == nullptr || partial_rows < cn_conv2d_bnstats_rows((long long)N * P * Q)) {
     cn_set_error("conv2d_fwd_bnstats: partial buffer of %d rows is too small", partial_rows);
@@ -1025,10 +1022,10 @@ extern "C" int cn_conv2d_fwd_bnstats(const void* x, const void* w_krsc, void* y,
 
 // The same with centred statistics: partial rows hold sum (y - pivot[c]) | sum (y - pivot[c])^2 (pivot: K floats,
 // normally the running mean of the BatchNorm that consumes y; cn_bn_fwd_train_partials_centered un-centres them).
-extern "C" int cn_conv2d_fwd_bnstats_centered(const void* x, const void* w_krsc, void* y, const float* bias, int N,
-                                              int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
-                                              int pad_h, int pad_w, int dtype, int relu, float* partial,
-                                              int partial_rows, const float* pivot, void* stream) {
+extern "C" cn_status cn_conv2d_fwd_bnstats_centered(const void* x, const void* w_krsc, void* y, const float* bias, int N,
+                                                    int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
+                                                    int pad_h, int pad_w, int dtype, int relu, float* partial,
+                                                    int partial_rows, const float* pivot, void* stream) {
   const long long P = (H + 2 * pad_h - R) / stride_h + 1, Q = (W + 2 * pad_w - S) / stride_w + 1;
   if (partial == nullptr || pivot == nullptr || partial_rows < cn_conv2d_bnstats_rows((long long)N * P * Q)) {
     cn_set_error("conv2d_fwd_bnstats_centered: needs a pivot and a partial buffer of enough rows (%d given)", partial_rows);
@@ -1046,10 +1043,10 @@ extern "C" int cn_conv2d_fwd_bnstats_centered(const void* x, const void* w_krsc,
 // by cn_conv2d_fwd_bnstats, without that pass (read y, read res, write z) and without this convolution's re-read of z.
 // stats / res_stats: the 4*C floats of cn_bn_fwd_train* (z = NULL).  partial (optional) as cn_conv2d_fwd_bnstats
 // (pivot optional: centred sums).
-extern "C" int cn_conv2d_fwd_lazyz(const void* bn_y, const void* res, const float* stats, const float* res_stats,
-                                   int relu, void* z, unsigned char* z_mask, const void* w_krsc, void* y, int N, int H,
-                                   int W, int C, int K, int dtype, float* partial, int partial_rows, const float* pivot,
-                                   void* stream) {
+extern "C" cn_status cn_conv2d_fwd_lazyz(const void* bn_y, const void* res, const float* stats, const float* res_stats,
+                                         int relu, void* z, unsigned char* z_mask, const void* w_krsc, void* y, int N, int H,
+                                         int W, int C, int K, int dtype, float* partial, int partial_rows, const float* pivot,
+                                         void* stream) {
   if (bn_y == nullptr || res == nullptr || stats == nullptr || z == nullptr) { cn_set_error("conv2d_fwd_lazyz: null operand"); return CN_EINVAL; }
   if (K > 128) { cn_set_error("conv2d_fwd_lazyz: %d output channels > 128 (one channel tile)", K); return CN_ESHAPE; }
   if (partial != nullptr && partial_rows < cn_conv2d_bnstats_rows((long long)N * H * W)) {
@@ -1140,38 +1137,32 @@ static int ig_conv_dgrad(const void* dy, const void* w_crsk, void* dx, const voi
   return CN_OK;
 }
 
-extern "C" int cn_conv2d_dgrad(const void* dy, const void* w_crsk, void* dx, const void* addend, int N, int H,
-                               int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
-                               int pad_w, int dtype, int out_f32, void* stream) {
-  return ig_conv_dgrad(dy, w_crsk, dx, addend, N, H, W, C, K, R, S, stride_h, stride_w, pad_h, pad_w, dtype,
-                       out_f32, nullptr, stream);
-}
-
 // "Lazy dy" data gradient (round 3): the upstream gradient dy is the result of a training-mode BatchNorm backward,
 //     dy[m][k] = c1[k]*g[m][k] + c2[k]*y[m][k] + c3[k]      (cn_bn_bwd_partials with dy = NULL leaves coef = [c1 | c2 | c3]),
 // and is formed on the operand load from g (the masked gradient w.r.t. the BatchNorm output) and y (the BatchNorm
 // input), with the operation order and rounding of the apply kernel: the same bits as cn_bn_bwd_partials(dy) followed
-// by cn_conv2d_dgrad(dy), without writing / re-reading dy.  K <= 512 channels, no epilogue operands.
-extern "C" int cn_conv2d_dgrad_lazy(const void* g, const void* bn_y, const float* coef, const void* w_crsk, void* dx,
-                                    int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
-                                    int pad_w, int dtype, void* stream) {
+// by cn_conv2d_dgrad_sa(dy), without writing / re-reading dy.  K <= 512 channels, no epilogue operands.
+extern "C" cn_status cn_conv2d_dgrad_lazy(const void* g, const void* bn_y, const float* coef, const void* w_crsk, void* dx,
+                                          int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
+                                          int pad_w, int dtype, void* stream) {
   if (g == nullptr || bn_y == nullptr || coef == nullptr) { cn_set_error("conv2d_dgrad_lazy: needs g, y and the coefficients"); return CN_EINVAL; }
   if (K > IG_XF_MAX) { cn_set_error("conv2d_dgrad_lazy: %d gradient channels > %d", K, IG_XF_MAX); return CN_ESHAPE; }
   return ig_conv_dgrad(g, w_crsk, dx, nullptr, N, H, W, C, K, R, S, stride_h, stride_w, pad_h, pad_w, dtype, 0, nullptr,
                        stream, 1, bn_y, coef);
 }
 
-// The same with a SUBSAMPLED addend: `addend` is [N][(H+1)/2][(W+1)/2][C], the values at the even (h, w) pixels of a
-// tensor that is zero everywhere else - the input gradient of a stride-2 1x1 projection (models/resnet.py:176-181),
-// which is what meets this gradient at the block input.  Saves writing and re-reading the three quarters of zeros.
-extern "C" int cn_conv2d_dgrad_sa(const void* dy, const void* w_crsk, void* dx, const void* addend, int addend_sub, int N,
-                                  int H, int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
-                                  int pad_w, int dtype, int out_f32, void* stream) {
+// The data gradient with an optional addend (dx += addend).  addend_sub = 2, a SUBSAMPLED addend: `addend` is
+// [N][(H+1)/2][(W+1)/2][C], the values at the even (h, w) pixels of a tensor that is zero everywhere else - the input
+// gradient of a stride-2 1x1 projection (models/resnet.py:176-181), which is what meets this gradient at the block
+// input.  Saves writing and re-reading the three quarters of zeros.
+extern "C" cn_status cn_conv2d_dgrad_sa(const void* dy, const void* w_crsk, void* dx, const void* addend, int addend_sub, int N,
+                                        int H, int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
+                                        int pad_w, int dtype, int out_f32, void* stream) {
   return ig_conv_dgrad(dy, w_crsk, dx, addend, N, H, W, C, K, R, S, stride_h, stride_w, pad_h, pad_w, dtype,
                        out_f32, nullptr, stream, addend_sub);
 }
 
-// Partial rows cn_conv2d_dgrad_bnbwd writes: one per 128-pixel tile of every
+// Partial rows cn_conv2d_dgrad_bnbwd_sa writes: one per 128-pixel tile of every
 // output-parity class.
 extern "C" int cn_conv2d_dgrad_bnbwd_rows(int N, int H, int W, int C, int stride_h, int stride_w) {
   int rows = 0;
@@ -1190,11 +1181,12 @@ extern "C" int cn_conv2d_dgrad_bnbwd_rows(int N, int H, int W, int C, int stride
 // (mask from `bn_mask` bits, or recomputed from bn_y*scale+shift > 0 when bn_relu and no mask) and
 // writes partial[row] = [sum g | sum g*(bn_y-mean)*invstd] per 128-pixel tile
 // (cn_conv2d_dgrad_bnbwd_rows rows of 2*C floats) for cn_bn_bwd_partials.  bn_coef = the 4*C floats
-// [mean | invstd | scale | shift] cn_bn_fwd_train wrote.
-static int dgrad_bnbwd_impl(const void* dy, const void* w_crsk, void* g, const void* addend, int addend_sub, int N,
-                            int H, int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
-                            int dtype, const void* bn_y, const unsigned char* bn_mask, const float* bn_coef,
-                            int bn_relu, float* partial, int partial_rows, void* stream) {
+// [mean | invstd | scale | shift] cn_bn_fwd_train wrote.  addend / addend_sub as cn_conv2d_dgrad_sa.
+extern "C" cn_status cn_conv2d_dgrad_bnbwd_sa(const void* dy, const void* w_crsk, void* g, const void* addend, int addend_sub,
+                                              int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
+                                              int pad_h, int pad_w, int dtype, const void* bn_y,
+                                              const unsigned char* bn_mask, const float* bn_coef, int bn_relu,
+                                              float* partial, int partial_rows, void* stream) {
   const int CH = cn_dtype_chunk(dtype);
   if (bn_y == nullptr || bn_coef == nullptr || partial == nullptr || C % CH != 0) {
     cn_set_error("conv2d_dgrad_bnbwd: needs bn_y, bn_coef, partial and C (%d) a multiple of %d", C, CH);
@@ -1205,23 +1197,4 @@ static int dgrad_bnbwd_impl(const void* dy, const void* w_crsk, void* g, const v
   bn.rows_cap = partial_rows;
   return ig_conv_dgrad(dy, w_crsk, g, addend, N, H, W, C, K, R, S, stride_h, stride_w, pad_h, pad_w, dtype, 0, &bn,
                        stream, addend_sub);
-}
-
-extern "C" int cn_conv2d_dgrad_bnbwd(const void* dy, const void* w_crsk, void* g, const void* addend, int N, int H,
-                                     int W, int C, int K, int R, int S, int stride_h, int stride_w, int pad_h,
-                                     int pad_w, int dtype, const void* bn_y, const unsigned char* bn_mask,
-                                     const float* bn_coef, int bn_relu, float* partial, int partial_rows,
-                                     void* stream) {
-  return dgrad_bnbwd_impl(dy, w_crsk, g, addend, 1, N, H, W, C, K, R, S, stride_h, stride_w, pad_h, pad_w, dtype, bn_y,
-                          bn_mask, bn_coef, bn_relu, partial, partial_rows, stream);
-}
-
-// ... with a subsampled addend (see cn_conv2d_dgrad_sa)
-extern "C" int cn_conv2d_dgrad_bnbwd_sa(const void* dy, const void* w_crsk, void* g, const void* addend, int addend_sub,
-                                        int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
-                                        int pad_h, int pad_w, int dtype, const void* bn_y,
-                                        const unsigned char* bn_mask, const float* bn_coef, int bn_relu,
-                                        float* partial, int partial_rows, void* stream) {
-  return dgrad_bnbwd_impl(dy, w_crsk, g, addend, addend_sub, N, H, W, C, K, R, S, stride_h, stride_w, pad_h, pad_w, dtype,
-                          bn_y, bn_mask, bn_coef, bn_relu, partial, partial_rows, stream);
 }

@@ -6,7 +6,7 @@
 // loss.backward(), trainer.py:162): the gradient of conv1's input, dx = dy1 * W, is added to the gradient arriving over
 // the shortcut; the sum is masked by the ReLU of the junction that produced the block input; the result g is the
 // upstream gradient of that junction's BatchNorm, whose backward needs sum(g) and sum(g * xhat) per channel.
-// cn_conv2d_dgrad_bnbwd(_sa) does all of that in the epilogue of the tiled implicit-GEMM kernel.  That kernel is a GEMM
+// cn_conv2d_dgrad_bnbwd_sa does all of that in the epilogue of the tiled implicit-GEMM kernel.  That kernel is a GEMM
 // kernel: one 128 x 128 output tile per workgroup, half a dozen workgroup barriers per tile, a fresh workgroup (launch,
 // index tables) every ~100 KB - and this operation is not a GEMM but a STREAM: per output element 2 bytes of addend, 2
 // of BatchNorm input, 2 of g and 1/8 of mask against 2*KD flops with KD = 64 ... 128, i.e. 6+ bytes per 128 - 256 flops.
@@ -460,9 +460,6 @@ extern "C" int cn_conv2d_dgrad_junction_ok(int C, int K, int dtype) {
   if ((C == 512 || C == 1024) && K == 256) return 1;
   return ((C == 256 && (K == 64 || K == 128)) || (C == 512 && K == 128)) ? 1 : 0;
 }
-extern "C" int cn_conv2d_dgrad_junction_rows(int N, int H, int W, int C) {   // (the K <= 128 forms)
-  return jd_plan((long long)N * H * W, jd_bm(C), nullptr);
-}
 // partial rows cn_conv2d_dgrad_junction writes for K -> C channels (the 256-channel reductions plan per channel slice)
 extern "C" int cn_conv2d_dgrad_junction_rows_k(int N, int H, int W, int C, int K) {
   return jd_plan((long long)N * H * W, jd_bm(C), nullptr, K >= 256 ? C / 256 : 1);
@@ -470,12 +467,12 @@ extern "C" int cn_conv2d_dgrad_junction_rows_k(int N, int H, int W, int C, int K
 
 // cn_conv2d_dgrad_bnbwd_sa for a 1x1 / stride-1 / unpadded convolution with K -> C channels of an instantiated shape,
 // ReLU bits given (bn_mask) and an addend (dense, or addend_sub = 2: the even pixels of a stride-2 projection's
-// gradient), as one persistent streaming kernel (see the head of this file).  partial: cn_conv2d_dgrad_junction_rows
+// gradient), as one persistent streaming kernel (see the head of this file).  partial: cn_conv2d_dgrad_junction_rows_k
 // rows of 2*C floats for cn_bn_bwd_partials.  g: the bits of cn_conv2d_dgrad_bnbwd_sa.
-extern "C" int cn_conv2d_dgrad_junction(const void* dy, const void* w_crsk, void* g, const void* addend, int addend_sub,
-                                        int N, int H, int W, int C, int K, int dtype, const void* bn_y,
-                                        const unsigned char* bn_mask, const float* bn_coef, float* partial,
-                                        int partial_rows, void* stream) {
+extern "C" cn_status cn_conv2d_dgrad_junction(const void* dy, const void* w_crsk, void* g, const void* addend, int addend_sub,
+                                              int N, int H, int W, int C, int K, int dtype, const void* bn_y,
+                                              const unsigned char* bn_mask, const float* bn_coef, float* partial,
+                                              int partial_rows, void* stream) {
   if (!cn_conv2d_dgrad_junction_ok(C, K, dtype)) { cn_set_error("conv2d_dgrad_junction: K=%d -> C=%d dtype %d is not an instantiated shape", K, C, dtype); return CN_ESHAPE; }
   if (dy == nullptr || w_crsk == nullptr || g == nullptr || addend == nullptr || bn_y == nullptr || bn_mask == nullptr ||
       bn_coef == nullptr || partial == nullptr) { cn_set_error("conv2d_dgrad_junction: null operand"); return CN_EINVAL; }
@@ -755,8 +752,8 @@ static int jfwd_impl(const char* who, const void* x, const float* xf, int relu, 
 #undef JF_GO
   return cn_check_launch("jfwd");
 }
-extern "C" int cn_conv1x1_stream_fwd(const void* x, const void* w_krsc, void* y, int N, int H, int W, int C, int K,
-                                     int dtype, float* partial, int partial_rows, void* stream) {
+extern "C" cn_status cn_conv1x1_stream_fwd(const void* x, const void* w_krsc, void* y, int N, int H, int W, int C, int K,
+                                           int dtype, float* partial, int partial_rows, void* stream) {
   return jfwd_impl("conv1x1_stream_fwd", x, nullptr, 0, nullptr, w_krsc, y, N, H, W, C, K, dtype, partial, partial_rows, stream);
 }
 // "Lazy a": cn_conv1x1_stream_fwd whose input is still the INPUT bn_y of the BatchNorm in front of the convolution
@@ -765,9 +762,9 @@ extern "C" int cn_conv1x1_stream_fwd(const void* x, const void* w_krsc, void* y,
 // it to a_out [M][C] (the convolution's saved input for the weight gradient), so the apply pass of an inner BatchNorm
 // (one read of bn_y + one write of a, then the convolution's read of a) becomes one read of bn_y + one write of a.
 // Same a and y bits as cn_bn_fwd_train's apply pass + cn_conv1x1_stream_fwd.
-extern "C" int cn_conv1x1_stream_fwd_lazya(const void* bn_y, const float* stats, int relu, void* a_out, const void* w_krsc,
-                                           void* y, int N, int H, int W, int C, int K, int dtype, float* partial,
-                                           int partial_rows, void* stream) {
+extern "C" cn_status cn_conv1x1_stream_fwd_lazya(const void* bn_y, const float* stats, int relu, void* a_out, const void* w_krsc,
+                                                 void* y, int N, int H, int W, int C, int K, int dtype, float* partial,
+                                                 int partial_rows, void* stream) {
   if (stats == nullptr || a_out == nullptr) { cn_set_error("conv1x1_stream_fwd_lazya: null operand"); return CN_EINVAL; }
   return jfwd_impl("conv1x1_stream_fwd_lazya", bn_y, stats + 2 * C, relu, a_out, w_krsc, y, N, H, W, C, K, dtype, partial,
                    partial_rows, stream);
@@ -912,8 +909,8 @@ extern "C" int cn_conv2d_dgrad_lazy_stream_ok(int C, int K, int dtype) {   // K 
 }
 // cn_conv2d_dgrad_lazy for a 1x1 / stride-1 convolution of an instantiated shape (512 -> 128 or 256 channels) as a
 // persistent streaming kernel.  Same bits.
-extern "C" int cn_conv2d_dgrad_lazy_stream(const void* g, const void* bn_y, const float* coef, const void* w_crsk, void* dx,
-                                           int N, int H, int W, int C, int K, int dtype, void* stream) {
+extern "C" cn_status cn_conv2d_dgrad_lazy_stream(const void* g, const void* bn_y, const float* coef, const void* w_crsk, void* dx,
+                                                 int N, int H, int W, int C, int K, int dtype, void* stream) {
   if (!cn_conv2d_dgrad_lazy_stream_ok(C, K, dtype)) { cn_set_error("conv2d_dgrad_lazy_stream: K=%d -> C=%d dtype %d is not an instantiated shape", K, C, dtype); return CN_ESHAPE; }
   if (g == nullptr || bn_y == nullptr || coef == nullptr || w_crsk == nullptr || dx == nullptr) { cn_set_error("conv2d_dgrad_lazy_stream: null operand"); return CN_EINVAL; }
   const long long M = (long long)N * H * W;

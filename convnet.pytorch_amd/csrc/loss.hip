@@ -90,9 +90,9 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* row_out, 
   }
 }
 
-extern "C" int cn_softmax_ce(const float* logits, const long long* target, void* dlogits, int grad_dtype,
-                             float* row_scratch, float* step_out, float* meters, int B, int K, float gscale,
-                             const float* gscale_dev, float smooth_eps, void* stream_) {
+extern "C" cn_status cn_softmax_ce(const float* logits, const long long* target, void* dlogits, int grad_dtype,
+                                   float* row_scratch, float* step_out, float* meters, int B, int K, float gscale,
+                                   const float* gscale_dev, float smooth_eps, void* stream_) {
   if (B <= 0 || K <= 0) { cn_set_error("softmax_ce: empty"); return CN_ESHAPE; }
   hipStream_t stream = (hipStream_t)stream_;
   if (dlogits != nullptr && grad_dtype == CN_BF16)

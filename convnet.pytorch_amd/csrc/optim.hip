@@ -262,9 +262,9 @@ static unsigned opt_grid(long long work, long long cap) {
   return (unsigned)nb;
 }
 
-extern "C" int cn_sgd_momentum(float* p, const float* g, float* buf, long long n, float lr, float momentum,
-                               float weight_decay, float gscale, const float* clip_coef, const float* hyper_dev,
-                               void* stream) {
+extern "C" cn_status cn_sgd_momentum(float* p, const float* g, float* buf, long long n, float lr, float momentum,
+                                     float weight_decay, float gscale, const float* clip_coef, const float* hyper_dev,
+                                     void* stream) {
   if (n <= 0) return CN_OK;
   if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) != 0) {
     cn_set_error("sgd_momentum: buffers must be 16-byte aligned");
@@ -278,8 +278,8 @@ extern "C" int cn_sgd_momentum(float* p, const float* g, float* buf, long long n
 #define CN_NORM_PARTS 1024
 extern "C" size_t cn_grad_norm_workspace(void) { return CN_NORM_PARTS * sizeof(float); }
 
-extern "C" int cn_grad_norm_clip(const float* g, long long n, float gscale, float max_norm, float* out2,
-                                 float* meters2, float meter_weight, float* workspace, void* stream_) {
+extern "C" cn_status cn_grad_norm_clip(const float* g, long long n, float gscale, float max_norm, float* out2,
+                                       float* meters2, float meter_weight, float* workspace, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   unsigned nb = opt_grid(n, CN_NORM_PARTS);
   CN_LAUNCH(sumsq_kernel, dim3(nb), dim3(256), stream, g, n, workspace);
@@ -288,8 +288,8 @@ extern "C" int cn_grad_norm_clip(const float* g, long long n, float gscale, floa
   return cn_check_launch("grad_norm_clip");
 }
 
-extern "C" int cn_weight_prep(const float* w_master, void* w_krsc, void* w_crsk, int Co, int taps, int Creal,
-                              int Cpad, int dtype, void* stream_) {
+extern "C" cn_status cn_weight_prep(const float* w_master, void* w_krsc, void* w_crsk, int Co, int taps, int Creal,
+                                    int Cpad, int dtype, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (Cpad < Creal || (w_crsk != nullptr && Cpad != Creal)) {
     cn_set_error("weight_prep: bad channel padding (Creal=%d Cpad=%d)", Creal, Cpad);
@@ -302,8 +302,8 @@ extern "C" int cn_weight_prep(const float* w_master, void* w_krsc, void* w_crsk,
   return cn_check_launch("weight_prep");
 }
 
-extern "C" int cn_weight_prep_multi(const float* master, void* wbuf, const long long* desc, int nd, long long total,
-                                    int dtype, void* stream_) {
+extern "C" cn_status cn_weight_prep_multi(const float* master, void* wbuf, const long long* desc, int nd, long long total,
+                                          int dtype, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (nd <= 0 || total <= 0) return CN_OK;
   dim3 grid(opt_grid(total, 8192));
@@ -312,8 +312,8 @@ extern "C" int cn_weight_prep_multi(const float* master, void* wbuf, const long 
   return cn_check_launch("weight_prep_multi");
 }
 
-extern "C" int cn_weight_prep_tiled(const float* master, void* wbuf, const long long* desc, const int* tiles,
-                                    int ntiles, int dtype, void* stream_) {
+extern "C" cn_status cn_weight_prep_tiled(const float* master, void* wbuf, const long long* desc, const int* tiles,
+                                          int ntiles, int dtype, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (ntiles <= 0) return CN_OK;
   if (!cn_dtype_ok(dtype)) { cn_set_error("weight_prep_tiled: bad dtype"); return CN_EINVAL; }
@@ -322,7 +322,7 @@ extern "C" int cn_weight_prep_tiled(const float* master, void* wbuf, const long 
   return cn_check_launch("weight_prep_tiled");
 }
 
-extern "C" int cn_weight_prep_pairs(const float* master_krsc, void* out, int K, int R, int S, int C, void* stream) {
+extern "C" cn_status cn_weight_prep_pairs(const float* master_krsc, void* out, int K, int R, int S, int C, void* stream) {
   if (K <= 0 || R <= 0 || S <= 0 || C < 1 || C > 4) { cn_set_error("weight_prep_pairs: need 1 <= C <= 4"); return CN_ESHAPE; }
   const int S2 = (S + 1) / 2;
   CN_LAUNCH(weight_prep_pairs_kernel, dim3(opt_grid((long long)K * R * S2 * 8, 256)), dim3(256), (hipStream_t)stream,
@@ -330,8 +330,8 @@ extern "C" int cn_weight_prep_pairs(const float* master_krsc, void* out, int K, 
   return cn_check_launch("weight_prep_pairs");
 }
 
-extern "C" int cn_wgrad_unpack_pairs(const float* packed, float* dw_krsc, int K, int R, int S, int C, float beta,
-                                     void* stream) {
+extern "C" cn_status cn_wgrad_unpack_pairs(const float* packed, float* dw_krsc, int K, int R, int S, int C, float beta,
+                                           void* stream) {
   if (K <= 0 || R <= 0 || S <= 0 || C < 1 || C > 4) { cn_set_error("wgrad_unpack_pairs: need 1 <= C <= 4"); return CN_ESHAPE; }
   const int S2 = (S + 1) / 2;
   CN_LAUNCH(wgrad_unpack_pairs_kernel, dim3(opt_grid((long long)K * R * S * C, 256)), dim3(256), (hipStream_t)stream,
@@ -342,8 +342,8 @@ extern "C" int cn_wgrad_unpack_pairs(const float* packed, float* dw_krsc, int K,
 #define CN_COLSUM_PARTS 64
 extern "C" size_t cn_colsum_workspace(int C) { return (size_t)CN_COLSUM_PARTS * C * sizeof(float); }
 
-extern "C" int cn_colsum(const void* x, float* out, int M, int C, int dtype, float beta, float scale,
-                         float* workspace, void* stream_) {
+extern "C" cn_status cn_colsum(const void* x, float* out, int M, int C, int dtype, float beta, float scale,
+                               float* workspace, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (M <= 0 || C <= 0) { cn_set_error("colsum: empty"); return CN_ESHAPE; }
   int parts = M < CN_COLSUM_PARTS ? M : CN_COLSUM_PARTS;
@@ -355,8 +355,8 @@ extern "C" int cn_colsum(const void* x, float* out, int M, int C, int dtype, flo
   return cn_check_launch("colsum");
 }
 
-extern "C" int cn_small_linear(int mode, const void* x, const float* w, const float* bias, void* out, float* dw,
-                               float* db, int B, int C, int K, int dtype, void* stream_) {
+extern "C" cn_status cn_small_linear(int mode, const void* x, const float* w, const float* bias, void* out, float* dw,
+                                     float* db, int B, int C, int K, int dtype, void* stream_) {
   // mode 0: out = y (fp32) from x;  1: out = dx (T) from x := dy (fp32);  2: dw/db += from x (T), out := dy (fp32)
   hipStream_t stream = (hipStream_t)stream_;
   if (B <= 0 || C <= 0 || K <= 0) { cn_set_error("small_linear: empty"); return CN_ESHAPE; }
@@ -378,7 +378,7 @@ extern "C" int cn_small_linear(int mode, const void* x, const float* w, const fl
   return cn_check_launch("small_linear");
 }
 
-extern "C" int cn_cast_from_f32(const float* x, void* y, long long n, int dtype, void* stream_) {
+extern "C" cn_status cn_cast_from_f32(const float* x, void* y, long long n, int dtype, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (n <= 0) return CN_OK;
   dim3 grid(opt_grid(n, 4096));
@@ -387,7 +387,7 @@ extern "C" int cn_cast_from_f32(const float* x, void* y, long long n, int dtype,
   return cn_check_launch("cast");
 }
 
-extern "C" int cn_fill_f32(float* x, long long n, float v, void* stream_) {
+extern "C" cn_status cn_fill_f32(float* x, long long n, float v, void* stream_) {
   if (n <= 0) return CN_OK;
   CN_LAUNCH(fill_kernel, dim3(opt_grid(n, 4096)), dim3(256), (hipStream_t)stream_, x, n, v);
   return cn_check_launch("fill");

@@ -472,11 +472,6 @@ extern "C" int cn_plan_set_input(void* plan, int slot, const void* base_) {
   return CN_OK;
 }
 
-// communicator entry points that really issue (comm.hip)
-int cn_comm_allreduce_bucket_issue(void* handle, float* buf, long long count, void* after_a, void* after_b, int n_after);
-int cn_comm_join_issue(void* handle, void* stream);
-int cn_comm_allreduce_issue(void* handle, void* buf, long long count, int dtype, void* stream);
-
 extern "C" int cn_plan_replay(void* plan) {
   Plan* p = (Plan*)plan;
   if (p == nullptr || !p->ended) { cn_set_error("cn_plan_replay: no finished plan"); return CN_EINVAL; }

@@ -315,8 +315,8 @@ static int pool_check(const char* who, int C, int dtype) {
     else CN_LAUNCH(kern<float>, grid, dim3(256), stream, __VA_ARGS__);                   \
   } while (0)
 
-extern "C" int cn_maxpool_fwd(const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, int k,
-                              int stride, int pad, int dtype, void* stream) {
+extern "C" cn_status cn_maxpool_fwd(const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, int k,
+                                    int stride, int pad, int dtype, void* stream) {
   int rc = pool_check("maxpool_fwd", C, dtype);
   if (rc) return rc;
   if (k * k > 255 || pad * 2 > k) { cn_set_error("maxpool_fwd: unsupported window"); return CN_ESHAPE; }
@@ -360,24 +360,24 @@ static int maxpool_fwd_bnrelu_impl(const void* x, const float* scale, const floa
   return cn_check_launch("maxpool_fwd_bnrelu");
 }
 
-extern "C" int cn_maxpool_fwd_bnrelu(const void* x, const float* scale, const float* shift, void* y,
-                                     unsigned char* idx, int N, int H, int W, int C, int k, int stride, int pad,
-                                     int dtype, void* stream) {
+extern "C" cn_status cn_maxpool_fwd_bnrelu(const void* x, const float* scale, const float* shift, void* y,
+                                           unsigned char* idx, int N, int H, int W, int C, int k, int stride, int pad,
+                                           int dtype, void* stream) {
   return maxpool_fwd_bnrelu_impl(x, scale, shift, y, idx, nullptr, N, H, W, C, k, stride, pad, dtype, stream);
 }
 
 // The same pass, additionally storing the pre-BatchNorm value of every winning tap (xmax, shaped like y): with it the
 // BatchNorm-backward sums of the fused stem are taken over the pooled map (cn_bn_bwd_maxpool_xmax) instead of the
 // 4x larger input map with the pool's gather per pixel.
-extern "C" int cn_maxpool_fwd_bnrelu_xmax(const void* x, const float* scale, const float* shift, void* y,
-                                          unsigned char* idx, void* xmax, int N, int H, int W, int C, int k,
-                                          int stride, int pad, int dtype, void* stream) {
+extern "C" cn_status cn_maxpool_fwd_bnrelu_xmax(const void* x, const float* scale, const float* shift, void* y,
+                                                unsigned char* idx, void* xmax, int N, int H, int W, int C, int k,
+                                                int stride, int pad, int dtype, void* stream) {
   if (xmax == nullptr) { cn_set_error("maxpool_fwd_bnrelu_xmax: no xmax buffer"); return CN_EINVAL; }
   return maxpool_fwd_bnrelu_impl(x, scale, shift, y, idx, xmax, N, H, W, C, k, stride, pad, dtype, stream);
 }
 
-extern "C" int cn_maxpool_bwd(const void* dy, const unsigned char* idx, void* dx, int N, int H, int W, int C,
-                              int k, int stride, int pad, int dtype, void* stream) {
+extern "C" cn_status cn_maxpool_bwd(const void* dy, const unsigned char* idx, void* dx, int N, int H, int W, int C,
+                                    int k, int stride, int pad, int dtype, void* stream) {
   int rc = pool_check("maxpool_bwd", C, dtype);
   if (rc) return rc;
   const int P = (H + 2 * pad - k) / stride + 1, Q = (W + 2 * pad - k) / stride + 1;
@@ -390,7 +390,7 @@ extern "C" int cn_maxpool_bwd(const void* dy, const unsigned char* idx, void* dx
   return cn_check_launch("maxpool_bwd");
 }
 
-extern "C" int cn_avgpool_fwd(const void* x, void* y, int N, int HW, int C, int dtype, void* stream) {
+extern "C" cn_status cn_avgpool_fwd(const void* x, void* y, int N, int HW, int C, int dtype, void* stream) {
   int rc = pool_check("avgpool_fwd", C, dtype);
   if (rc) return rc;
   const int CH = cn_dtype_chunk(dtype);
@@ -399,7 +399,7 @@ extern "C" int cn_avgpool_fwd(const void* x, void* y, int N, int HW, int C, int 
   return cn_check_launch("avgpool_fwd");
 }
 
-extern "C" int cn_avgpool_bwd(const void* dy, void* dx, int N, int HW, int C, int dtype, void* stream) {
+extern "C" cn_status cn_avgpool_bwd(const void* dy, void* dx, int N, int HW, int C, int dtype, void* stream) {
   int rc = pool_check("avgpool_bwd", C, dtype);
   if (rc) return rc;
   const int CH = cn_dtype_chunk(dtype);
@@ -426,8 +426,8 @@ __global__ __launch_bounds__(256) void u8_nhwc_to_nchw_lut_kernel(const unsigned
     for (int c = 0; c < C; ++c) y[(n * C + c) * (long long)HW + hw] = s_lut[c * 256 + px[c]];
   }
 }
-extern "C" int cn_u8_nhwc_to_nchw_lut(const unsigned char* x_nhwc, float* y_nchw, int N, int H, int W, int C,
-                                      const float* lut, void* stream) {
+extern "C" cn_status cn_u8_nhwc_to_nchw_lut(const unsigned char* x_nhwc, float* y_nchw, int N, int H, int W, int C,
+                                            const float* lut, void* stream) {
   if (x_nhwc == nullptr || y_nchw == nullptr || lut == nullptr) { cn_set_error("u8_nhwc_to_nchw_lut: null operand"); return CN_EINVAL; }
   if (N <= 0 || H <= 0 || W <= 0 || C < 1 || C > 4) { cn_set_error("u8_nhwc_to_nchw_lut: bad shape (C = %d, 1..4)", C); return CN_ESHAPE; }
   const long long npix = (long long)N * H * W;
@@ -437,8 +437,8 @@ extern "C" int cn_u8_nhwc_to_nchw_lut(const unsigned char* x_nhwc, float* y_nchw
   return cn_check_launch("u8_nhwc_to_nchw_lut");
 }
 
-extern "C" int cn_nchw_to_nhwc(const float* x, void* y, int N, int C, int H, int W, int Cpad, int dtype,
-                               void* stream) {
+extern "C" cn_status cn_nchw_to_nhwc(const float* x, void* y, int N, int C, int H, int W, int Cpad, int dtype,
+                                     void* stream) {
   int rc = pool_check("nchw_to_nhwc", Cpad, dtype);
   if (rc) return rc;
   if (Cpad < C) { cn_set_error("nchw_to_nhwc: Cpad < C"); return CN_ESHAPE; }
@@ -448,8 +448,8 @@ extern "C" int cn_nchw_to_nhwc(const float* x, void* y, int N, int C, int H, int
   return cn_check_launch("nchw_to_nhwc");
 }
 
-extern "C" int cn_nchw_to_pairs(const float* x, void* y, int N, int C, int H, int W, int pad_h, int pad_w,
-                                void* stream) {
+extern "C" cn_status cn_nchw_to_pairs(const float* x, void* y, int N, int C, int H, int W, int pad_h, int pad_w,
+                                      void* stream) {
   if (C < 1 || C > 4 || N <= 0 || H <= 0 || W <= 0 || pad_h < 0 || pad_w < 0 || ((W + 2 * pad_w) & 1)) {
     cn_set_error("nchw_to_pairs: need 1 <= C <= 4 and an even padded width (C=%d, W=%d, pad_w=%d)", C, W, pad_w);
     return CN_ESHAPE;
@@ -460,8 +460,8 @@ extern "C" int cn_nchw_to_pairs(const float* x, void* y, int N, int C, int H, in
   return cn_check_launch("nchw_to_pairs");
 }
 
-extern "C" int cn_nhwc_to_nchw(const void* x, float* y, int N, int C, int H, int W, int Cpad, int dtype,
-                               void* stream) {
+extern "C" cn_status cn_nhwc_to_nchw(const void* x, float* y, int N, int C, int H, int W, int Cpad, int dtype,
+                                     void* stream) {
   if (!cn_dtype_ok(dtype)) { cn_set_error("nhwc_to_nchw: bad dtype"); return CN_EINVAL; }
   dim3 grid(pool_grid((long long)N * C * H * W));
   POOL_DISPATCH(nhwc_to_nchw_kernel, grid, (hipStream_t)stream, (const char*)x, y, N, C, H * W, Cpad);
@@ -469,7 +469,7 @@ extern "C" int cn_nhwc_to_nchw(const void* x, float* y, int N, int C, int H, int
 }
 
 // op: 0  a += b;  1  a = relu(b);  2  a = b * (c > 0);  3  a = b * c.   n = element count (multiple of the chunk).
-extern "C" int cn_eltwise(int op, void* a, const void* b, const void* c, long long n, int dtype, void* stream) {
+extern "C" cn_status cn_eltwise(int op, void* a, const void* b, const void* c, long long n, int dtype, void* stream) {
   if (!cn_dtype_ok(dtype)) { cn_set_error("eltwise: bad dtype"); return CN_EINVAL; }
   const int CH = cn_dtype_chunk(dtype);
   if (n % CH != 0) { cn_set_error("eltwise: n=%lld not a multiple of %d", n, CH); return CN_ESHAPE; }

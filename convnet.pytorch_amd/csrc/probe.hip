@@ -65,19 +65,19 @@ __global__ __launch_bounds__(64) void probe_tr16_kernel(const unsigned short* sr
   for (int j = 0; j < 4; ++j) out[l * 4 + j] = (unsigned short)v[j];
 }
 
-extern "C" int cn_probe_mfma_bf16(const unsigned short* A, const unsigned short* B, float* D, void* stream) {
+extern "C" cn_status cn_probe_mfma_bf16(const unsigned short* A, const unsigned short* B, float* D, void* stream) {
   CN_LAUNCH(probe_mfma_bf16_kernel, dim3(1), dim3(64), (hipStream_t)stream, A, B, D);
   return cn_check_launch("probe_mfma_bf16");
 }
-extern "C" int cn_probe_mfma_f16(const unsigned short* A, const unsigned short* B, float* D, void* stream) {
+extern "C" cn_status cn_probe_mfma_f16(const unsigned short* A, const unsigned short* B, float* D, void* stream) {
   CN_LAUNCH(probe_mfma_f16_kernel, dim3(1), dim3(64), (hipStream_t)stream, A, B, D);
   return cn_check_launch("probe_mfma_f16");
 }
-extern "C" int cn_probe_mfma_f32(const float* A, const float* B, float* D, void* stream) {
+extern "C" cn_status cn_probe_mfma_f32(const float* A, const float* B, float* D, void* stream) {
   CN_LAUNCH(probe_mfma_f32_kernel, dim3(1), dim3(64), (hipStream_t)stream, A, B, D);
   return cn_check_launch("probe_mfma_f32");
 }
-extern "C" int cn_probe_tr16(const unsigned short* src, unsigned short* out, void* stream) {
+extern "C" cn_status cn_probe_tr16(const unsigned short* src, unsigned short* out, void* stream) {
   CN_LAUNCH(probe_tr16_kernel, dim3(1), dim3(64), (hipStream_t)stream, src, out);
   return cn_check_launch("probe_tr16");
 }

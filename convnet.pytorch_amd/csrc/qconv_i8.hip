@@ -379,11 +379,11 @@ static unsigned qi_grid(long long items) {
 // Activation (NHWC, dtype) -> int8 levels - 128 plus the per-output-pixel window sums / border classes of a
 // convolution with the given geometry.  chansum: scratch int32 [N*H*W].  rowcls[P] / colcls[Q]: host-enumerated
 // class ids of every output row / column (DEVICE arrays).
-extern "C" int cn_i8_prepare_activation(const void* x, signed char* q, int* chansum, int* A, unsigned char* cls, int N,
-                                        int H, int W, int C, int R, int S, int stride_h, int stride_w, int pad_h,
-                                        int pad_w, int dtype, const float* zero_point, const float* range,
-                                        const unsigned char* rowcls, const unsigned char* colcls, int ncolcls,
-                                        void* stream_) {
+extern "C" cn_status cn_i8_prepare_activation(const void* x, signed char* q, int* chansum, int* A, unsigned char* cls, int N,
+                                              int H, int W, int C, int R, int S, int stride_h, int stride_w, int pad_h,
+                                              int pad_w, int dtype, const float* zero_point, const float* range,
+                                              const unsigned char* rowcls, const unsigned char* colcls, int ncolcls,
+                                              void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (x == nullptr || q == nullptr || chansum == nullptr || A == nullptr || cls == nullptr || zero_point == nullptr ||
       range == nullptr || rowcls == nullptr || colcls == nullptr) { cn_set_error("i8_prepare_activation: null operand"); return CN_EINVAL; }
@@ -403,8 +403,8 @@ extern "C" int cn_i8_prepare_activation(const void* x, signed char* q, int* chan
 }
 
 // fp32 master filter [K][taps][C] -> int8 levels - 128 (same memory order), wsum[K][taps], wpar[K][2] = {scale, zero'}
-extern "C" int cn_i8_prepare_weight(const float* w_master, signed char* q, int* wsum, float* wpar, int K, int taps, int C,
-                                    void* stream) {
+extern "C" cn_status cn_i8_prepare_weight(const float* w_master, signed char* q, int* wsum, float* wpar, int K, int taps, int C,
+                                          void* stream) {
   if (w_master == nullptr || q == nullptr || wsum == nullptr || wpar == nullptr || K <= 0 || taps <= 0 || C <= 0) {
     cn_set_error("i8_prepare_weight: bad arguments");
     return CN_EINVAL;
@@ -415,11 +415,11 @@ extern "C" int cn_i8_prepare_weight(const float* w_master, signed char* q, int* 
 
 // y[N,P,Q,K] (dtype, or fp32 when out_f32) = the reference's QConv2d forward product, evaluated on the int8
 // matrix cores.  tables: scratch of (2 + ncls) * K floats (alpha | beta | gamma).
-extern "C" int cn_conv2d_fwd_i8(const signed char* xq, const signed char* wq, void* y, const int* A,
-                                const unsigned char* cls, const float* zero_point, const float* range, const float* wpar,
-                                const int* wsum, const unsigned char* clsmask, int ncls, float* tables, int N, int H, int W,
-                                int C, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int out_dtype,
-                                void* stream_) {
+extern "C" cn_status cn_conv2d_fwd_i8(const signed char* xq, const signed char* wq, void* y, const int* A,
+                                      const unsigned char* cls, const float* zero_point, const float* range, const float* wpar,
+                                      const int* wsum, const unsigned char* clsmask, int ncls, float* tables, int N, int H, int W,
+                                      int C, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int out_dtype,
+                                      void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int P = (H + 2 * pad_h - R) / stride_h + 1, Q = (W + 2 * pad_w - S) / stride_w + 1;
   if (P <= 0 || Q <= 0 || N <= 0) { cn_set_error("conv2d_fwd_i8: empty output"); return CN_ESHAPE; }
@@ -476,7 +476,7 @@ __global__ void qi_probe_kernel(const signed char* A, const signed char* B, int*
   c = cn_mfma_32x32x32_i8(a.v, b.v, c);
   for (int r = 0; r < 16; ++r) D[((r & 3) + 8 * (r >> 2) + 4 * (l >> 5)) * 32 + (l & 31)] = c[r];
 }
-extern "C" int cn_probe_mfma_i8(const signed char* A, const signed char* B, int* D, void* stream) {
+extern "C" cn_status cn_probe_mfma_i8(const signed char* A, const signed char* B, int* D, void* stream) {
   CN_LAUNCH(qi_probe_kernel, dim3(1), dim3(64), (hipStream_t)stream, A, B, D);
   return cn_check_launch("probe_mfma_i8");
 }

@@ -121,8 +121,8 @@ extern "C" size_t cn_minmax_workspace(int rows, long long row_len) {
 
 // Per-row minimum / maximum of `rows` contiguous rows of `row_len` elements: minmax[r] = {min, max}.
 // (calculate_qparams' x.flatten(1).min(-1) / .max(-1), quantize.py:21-27.)
-extern "C" int cn_minmax_rows(const void* x, int rows, long long row_len, int dtype, float* minmax, float* ws,
-                              size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_minmax_rows(const void* x, int rows, long long row_len, int dtype, float* minmax, float* ws,
+                                    size_t ws_bytes, void* stream_) {
   if (rows <= 0 || row_len <= 0 || x == nullptr || minmax == nullptr) { cn_set_error("minmax_rows: bad arguments"); return CN_EINVAL; }
   if (rows > 65535) { cn_set_error("minmax_rows: %d rows > 65535", rows); return CN_ESHAPE; }
   if (ws == nullptr || ws_bytes < cn_minmax_workspace(rows, row_len)) { cn_set_error("minmax_rows: workspace too small"); return CN_EWORKSPACE; }
@@ -188,8 +188,8 @@ __global__ __launch_bounds__(Q_NT) void qparams_kernel(const float* minmax, int 
   }
 }
 
-extern "C" int cn_qparams(const float* minmax, int rows, int mode, float* qp, float* running_zp, float* running_range,
-                          float momentum, void* stream) {
+extern "C" cn_status cn_qparams(const float* minmax, int rows, int mode, float* qp, float* running_zp, float* running_range,
+                                float momentum, void* stream) {
   if (minmax == nullptr || qp == nullptr || rows <= 0 || (mode != 0 && mode != 1)) { cn_set_error("qparams: bad arguments"); return CN_EINVAL; }
   if ((running_zp == nullptr) != (running_range == nullptr)) { cn_set_error("qparams: both running buffers or none"); return CN_EINVAL; }
   CN_LAUNCH(qparams_kernel, dim3(1), dim3(Q_NT), (hipStream_t)stream, minmax, rows, mode, qp, running_zp, running_range,
@@ -390,27 +390,27 @@ static int quantize_impl(const void* x, void* y, long long n, int dtype, const f
 }
 // cn_quantize_s storing the 8-bit LEVELS (one byte per element, element order kept) instead of the snapped values: the
 // consumer de-quantises on load with the same (zero_point, range) - cn_rangebn_bwd_q8.  value = T(level * scale + zp).
-extern "C" int cn_quantize_levels(const void* x, unsigned char* y8, long long n, int dtype, const float* zero_point,
-                                  const float* range, int num_bits, const float* noise, int stochastic,
-                                  unsigned long long seed, const unsigned long long* step_counter, void* stream_) {
+extern "C" cn_status cn_quantize_levels(const void* x, unsigned char* y8, long long n, int dtype, const float* zero_point,
+                                        const float* range, int num_bits, const float* noise, int stochastic,
+                                        unsigned long long seed, const unsigned long long* step_counter, void* stream_) {
   if (y8 == nullptr) { cn_set_error("quantize_levels: null output"); return CN_EINVAL; }
   return quantize_impl(x, nullptr, n, dtype, zero_point, range, num_bits, noise, stochastic, seed, step_counter, stream_, y8);
 }
-extern "C" int cn_quantize(const void* x, void* y, long long n, int dtype, const float* zero_point, const float* range,
-                           int num_bits, const float* noise, int stochastic, unsigned long long seed, void* stream_) {
+extern "C" cn_status cn_quantize(const void* x, void* y, long long n, int dtype, const float* zero_point, const float* range,
+                                 int num_bits, const float* noise, int stochastic, unsigned long long seed, void* stream_) {
   return quantize_impl(x, y, n, dtype, zero_point, range, num_bits, noise, stochastic, seed, nullptr, stream_);
 }
 // cn_quantize whose generator seed is `seed` mixed with a device-resident step counter (advanced by cn_counter_inc once
 // per training step): the launch can be captured into a HIP graph and still rounds with fresh noise on every replay.
-extern "C" int cn_quantize_s(const void* x, void* y, long long n, int dtype, const float* zero_point, const float* range,
-                             int num_bits, const float* noise, int stochastic, unsigned long long seed,
-                             const unsigned long long* step_counter, void* stream_) {
+extern "C" cn_status cn_quantize_s(const void* x, void* y, long long n, int dtype, const float* zero_point, const float* range,
+                                   int num_bits, const float* noise, int stochastic, unsigned long long seed,
+                                   const unsigned long long* step_counter, void* stream_) {
   return quantize_impl(x, y, n, dtype, zero_point, range, num_bits, noise, stochastic, seed, step_counter, stream_);
 }
 __global__ void counter_inc_kernel(unsigned long long* p) {
   if (threadIdx.x == 0 && blockIdx.x == 0) p[0] += 1ull;
 }
-extern "C" int cn_counter_inc(unsigned long long* counter, void* stream_) {
+extern "C" cn_status cn_counter_inc(unsigned long long* counter, void* stream_) {
   if (counter == nullptr) { cn_set_error("counter_inc: null"); return CN_EINVAL; }
   CN_LAUNCH(counter_inc_kernel, dim3(1), dim3(64), (hipStream_t)stream_, counter);
   return cn_check_launch("counter_inc");
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(Q_NT) void quantize_rows_kernel(const float* x, flo
   for (int e = tid; e < row_len; e += Q_NT) y[(size_t)r * row_len + e] = q_snap(row[e], mn, scale, qmax, 0.f);
 }
 
-extern "C" int cn_quantize_rows(const float* x, float* y, int rows, int row_len, int num_bits, void* stream) {
+extern "C" cn_status cn_quantize_rows(const float* x, float* y, int rows, int row_len, int num_bits, void* stream) {
   if (rows <= 0 || row_len <= 0) return CN_OK;
   if (x == nullptr || y == nullptr || num_bits < 1 || num_bits > 23) { cn_set_error("quantize_rows: bad arguments"); return CN_EINVAL; }
   CN_LAUNCH(quantize_rows_kernel, dim3((unsigned)rows), dim3(Q_NT), (hipStream_t)stream, x, y, row_len,
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(Q_NT) void quantize_rows_multi_kernel(const float* 
   for (int e = tid; e < row_len; e += Q_NT) y[off + e] = q_snap(row[e], mn, scale, qmax, 0.f);
 }
 
-extern "C" int cn_quantize_rows_multi(const float* x, float* y, const long long* rowtab, int rows, void* stream) {
+extern "C" cn_status cn_quantize_rows_multi(const float* x, float* y, const long long* rowtab, int rows, void* stream) {
   if (rows <= 0) return CN_OK;
   if (x == nullptr || y == nullptr || rowtab == nullptr) { cn_set_error("quantize_rows_multi: bad arguments"); return CN_EINVAL; }
   CN_LAUNCH(quantize_rows_multi_kernel, dim3((unsigned)rows), dim3(Q_NT), (hipStream_t)stream, x, y, rowtab);
@@ -871,10 +871,10 @@ static int rangebn_fwd_impl(const void* x, const void* residual, void* z, const 
   return cn_check_launch("rangebn_fwd");
 }
 
-extern "C" int cn_rangebn_fwd(const void* x, const void* residual, void* z, const float* weight, const float* bias,
-                              float* running_mean, float* running_var, float momentum, float eps, int chunks,
-                              float scale_fix, float* stats, int* arg, int M, int C, int relu, int training, int dtype,
-                              float* ws, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_rangebn_fwd(const void* x, const void* residual, void* z, const float* weight, const float* bias,
+                                    float* running_mean, float* running_var, float momentum, float eps, int chunks,
+                                    float scale_fix, float* stats, int* arg, int M, int C, int relu, int training, int dtype,
+                                    float* ws, size_t ws_bytes, void* stream_) {
   return rangebn_fwd_impl(x, residual, z, weight, bias, running_mean, running_var, momentum, eps, chunks, scale_fix, stats,
                           arg, M, C, relu, training, dtype, ws, ws_bytes, stream_, nullptr, 8, nullptr, 0, nullptr);
 }
@@ -883,11 +883,11 @@ extern "C" int cn_rangebn_fwd(const void* x, const void* residual, void* z, cons
 //     on load and stores the snapped tensor to qx_out (what cn_quantize would have written; the backward pass takes it);
 //   z_minmax (optional, mm_rows rows = batch samples): per-sample {min, max} of the stored z for the next quantiser.
 // Same qx, z, stats, arg bits as cn_quantize followed by cn_rangebn_fwd; z_minmax = cn_minmax_rows(z, mm_rows).
-extern "C" int cn_rangebn_fwd_q(const void* x, const float* x_qparams, int x_bits, void* qx_out, const void* residual, void* z,
-                                const float* weight, const float* bias, float* running_mean, float* running_var,
-                                float momentum, float eps, int chunks, float scale_fix, float* stats, int* arg, int M,
-                                int C, int relu, int dtype, int mm_rows, float* z_minmax, float* ws, size_t ws_bytes,
-                                void* stream_) {
+extern "C" cn_status cn_rangebn_fwd_q(const void* x, const float* x_qparams, int x_bits, void* qx_out, const void* residual, void* z,
+                                      const float* weight, const float* bias, float* running_mean, float* running_var,
+                                      float momentum, float eps, int chunks, float scale_fix, float* stats, int* arg, int M,
+                                      int C, int relu, int dtype, int mm_rows, float* z_minmax, float* ws, size_t ws_bytes,
+                                      void* stream_) {
   if (x_qparams == nullptr || x_bits < 1 || x_bits > 23 || qx_out == nullptr) { cn_set_error("rangebn_fwd_q: needs the input quantiser's parameters and qx_out"); return CN_EINVAL; }
   return rangebn_fwd_impl(x, residual, z, weight, bias, running_mean, running_var, momentum, eps, chunks, scale_fix, stats,
                           arg, M, C, relu, 1, dtype, ws, ws_bytes, stream_, x_qparams, x_bits, qx_out, mm_rows, z_minmax);
@@ -895,11 +895,11 @@ extern "C" int cn_rangebn_fwd_q(const void* x, const float* x_qparams, int x_bit
 
 // cn_rangebn_fwd_q with the snapped input kept as 8-bit LEVELS (qx8_out: one byte per element) instead of values: the same
 // z / stats / arg / z_minmax bits; the backward pass takes the levels and x_qparams (cn_rangebn_bwd_q8).  x_bits <= 8.
-extern "C" int cn_rangebn_fwd_q8(const void* x, const float* x_qparams, int x_bits, unsigned char* qx8_out, void* z,
-                                 const float* weight, const float* bias, float* running_mean, float* running_var,
-                                 float momentum, float eps, int chunks, float scale_fix, float* stats, int* arg, int M,
-                                 int C, int relu, int dtype, int mm_rows, float* z_minmax, float* ws, size_t ws_bytes,
-                                 void* stream_) {
+extern "C" cn_status cn_rangebn_fwd_q8(const void* x, const float* x_qparams, int x_bits, unsigned char* qx8_out, void* z,
+                                       const float* weight, const float* bias, float* running_mean, float* running_var,
+                                       float momentum, float eps, int chunks, float scale_fix, float* stats, int* arg, int M,
+                                       int C, int relu, int dtype, int mm_rows, float* z_minmax, float* ws, size_t ws_bytes,
+                                       void* stream_) {
   if (x_qparams == nullptr || x_bits < 1 || x_bits > 8 || qx8_out == nullptr) { cn_set_error("rangebn_fwd_q8: needs the <= 8-bit input quantiser's parameters and qx8_out"); return CN_EINVAL; }
   return rangebn_fwd_impl(x, nullptr, z, weight, bias, running_mean, running_var, momentum, eps, chunks, scale_fix, stats,
                           arg, M, C, relu, 1, dtype, ws, ws_bytes, stream_, x_qparams, x_bits, nullptr, mm_rows, z_minmax, qx8_out);
@@ -1182,17 +1182,17 @@ static int rangebn_bwd_impl(const void* g, const void* x, const float* weight, c
   return cn_check_launch("rangebn_bwd");
 }
 
-extern "C" int cn_rangebn_bwd(const void* g, const void* x, const float* weight, const float* stats, const int* arg,
-                              void* dx, float* dweight, float* dbias, int M, int C, int chunks, float scale_fix,
-                              int dtype, float* ws, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_rangebn_bwd(const void* g, const void* x, const float* weight, const float* stats, const int* arg,
+                                    void* dx, float* dweight, float* dbias, int M, int C, int chunks, float scale_fix,
+                                    int dtype, float* ws, size_t ws_bytes, void* stream_) {
   return rangebn_bwd_impl(g, x, weight, stats, arg, dx, dweight, dbias, M, C, chunks, scale_fix, dtype, ws, ws_bytes, stream_,
                           0, nullptr);
 }
 // cn_rangebn_bwd with the routing folded into the apply pass and dx_minmax[mm_rows][2] = cn_minmax_rows(dx, mm_rows) as a
 // side output (mm_rows = batch samples).  Same dx, dweight, dbias bits.
-extern "C" int cn_rangebn_bwd_mm(const void* g, const void* x, const float* weight, const float* stats, const int* arg,
-                                 void* dx, float* dweight, float* dbias, int M, int C, int chunks, float scale_fix,
-                                 int dtype, int mm_rows, float* dx_minmax, float* ws, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_rangebn_bwd_mm(const void* g, const void* x, const float* weight, const float* stats, const int* arg,
+                                       void* dx, float* dweight, float* dbias, int M, int C, int chunks, float scale_fix,
+                                       int dtype, int mm_rows, float* dx_minmax, float* ws, size_t ws_bytes, void* stream_) {
   if (dx_minmax == nullptr) { cn_set_error("rangebn_bwd_mm: needs dx_minmax"); return CN_EINVAL; }
   return rangebn_bwd_impl(g, x, weight, stats, arg, dx, dweight, dbias, M, C, chunks, scale_fix, dtype, ws, ws_bytes, stream_,
                           mm_rows, dx_minmax);
@@ -1203,10 +1203,10 @@ extern "C" int cn_rangebn_bwd_mm(const void* g, const void* x, const float* weig
 // means that operand holds values as before.  Same dx, dweight, dbias, dx_minmax bits as on the stored values.
 // dx_qp_extreme (optional, mm_rows <= 256): [zero_point, range] = cn_qparams(dx_minmax, mm_rows, 1), for the gradient quantiser
 // of the convolution in front.
-extern "C" int cn_rangebn_bwd_q8(const void* g, const float* g_qparams, int g_bits, const void* x, const float* x_qparams,
-                                 int x_bits, const float* weight, const float* stats, const int* arg, void* dx,
-                                 float* dweight, float* dbias, int M, int C, int chunks, float scale_fix, int dtype,
-                                 int mm_rows, float* dx_minmax, float* dx_qp_extreme, float* ws, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_rangebn_bwd_q8(const void* g, const float* g_qparams, int g_bits, const void* x, const float* x_qparams,
+                                       int x_bits, const float* weight, const float* stats, const int* arg, void* dx,
+                                       float* dweight, float* dbias, int M, int C, int chunks, float scale_fix, int dtype,
+                                       int mm_rows, float* dx_minmax, float* dx_qp_extreme, float* ws, size_t ws_bytes, void* stream_) {
   if (dx_minmax == nullptr) { cn_set_error("rangebn_bwd_q8: needs dx_minmax"); return CN_EINVAL; }
   if (dx_qp_extreme != nullptr && mm_rows > Q_NT) { cn_set_error("rangebn_bwd_q8: dx_qp_extreme needs mm_rows <= %d", Q_NT); return CN_ESHAPE; }
   return rangebn_bwd_impl(g, x, weight, stats, arg, dx, dweight, dbias, M, C, chunks, scale_fix, dtype, ws, ws_bytes, stream_,
@@ -1260,13 +1260,13 @@ extern "C" size_t cn_eltwise_mm_workspace(long long n, int rows, int dtype) {
 }
 static int eltwise_mm_impl(int op, void* a, const void* b, const void* c, long long n, int dtype, int rows, float* minmax,
                            float* qp_extreme, float* ws, size_t ws_bytes, void* stream_);
-extern "C" int cn_eltwise_mm(int op, void* a, const void* b, const void* c, long long n, int dtype, int rows, float* minmax,
-                             float* ws, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_eltwise_mm(int op, void* a, const void* b, const void* c, long long n, int dtype, int rows, float* minmax,
+                                   float* ws, size_t ws_bytes, void* stream_) {
   return eltwise_mm_impl(op, a, b, c, n, dtype, rows, minmax, nullptr, ws, ws_bytes, stream_);
 }
 // ... additionally qp_extreme[2] = cn_qparams(minmax, rows, 1) (rows <= 256): the consumer is a gradient quantiser
-extern "C" int cn_eltwise_mm_qp(int op, void* a, const void* b, const void* c, long long n, int dtype, int rows, float* minmax,
-                                float* qp_extreme, float* ws, size_t ws_bytes, void* stream_) {
+extern "C" cn_status cn_eltwise_mm_qp(int op, void* a, const void* b, const void* c, long long n, int dtype, int rows, float* minmax,
+                                      float* qp_extreme, float* ws, size_t ws_bytes, void* stream_) {
   if (qp_extreme == nullptr || rows > Q_NT) { cn_set_error("eltwise_mm_qp: needs qp_extreme and rows <= %d", Q_NT); return CN_EINVAL; }
   return eltwise_mm_impl(op, a, b, c, n, dtype, rows, minmax, qp_extreme, ws, ws_bytes, stream_);
 }

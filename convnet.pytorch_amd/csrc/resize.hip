@@ -70,9 +70,9 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const unsigned char* tmp,
 
 // B crops -> out[B][S][S][C] uint8.  total_rows = sum of the crops' heights (rows of tmp, which holds total_rows * S * C
 // bytes); row_owner[total_rows] / row_off[B] as above.  All tables and pixels are device memory.
-extern "C" int cn_resize_u8_crops(const unsigned char* pixels, const long long* meta, const int* tables, const int* row_owner,
-                                  const int* row_off, unsigned char* tmp, unsigned char* out, int B, int total_rows, int S,
-                                  int C, void* stream_) {
+extern "C" cn_status cn_resize_u8_crops(const unsigned char* pixels, const long long* meta, const int* tables, const int* row_owner,
+                                        const int* row_off, unsigned char* tmp, unsigned char* out, int B, int total_rows, int S,
+                                        int C, void* stream_) {
   if (pixels == nullptr || meta == nullptr || tables == nullptr || row_owner == nullptr || row_off == nullptr || tmp == nullptr ||
       out == nullptr) { cn_set_error("resize_u8_crops: null operand"); return CN_EINVAL; }
   if (B <= 0 || total_rows <= 0 || S <= 0 || C < 1 || C > 4) { cn_set_error("resize_u8_crops: bad shape"); return CN_ESHAPE; }

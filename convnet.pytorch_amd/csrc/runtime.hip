@@ -83,12 +83,10 @@ int cn_get_option(const char* name, int dflt) {
 // Cross-stream ordering without torch: `to` waits for everything queued on `from` so far.  Events come from a
 // ring created once (timing disabled, system-scope fence disabled: both streams are on this device, nothing here has to
 // become visible to the host).
-// launch plans (plan.hip) log the hand-offs below while one is being recorded
-void cn_plan_rec_fork(void* from, void* to);
-int cn_plan_rec_wait_mark(int handle, void* to);
+// launch plans (plan.hip) log the hand-offs below while one is being recorded (cn_plan_rec_fork / _wait_mark)
 
 #define CN_FORK_EVENTS 256
-extern "C" int cn_stream_fork(void* from_, void* to_) {
+extern "C" cn_status cn_stream_fork(void* from_, void* to_) {
 #ifdef CN_EMULATE
   if (cn_plan_recording) cn_plan_rec_fork(from_, to_);
   return CN_OK;
@@ -149,7 +147,7 @@ extern "C" int cn_stream_disarm(void) {
   return cn_tl_stop_recorded;
 #endif
 }
-extern "C" int cn_stream_wait_mark(int handle, void* to_stream) {
+extern "C" cn_status cn_stream_wait_mark(int handle, void* to_stream) {
 #ifdef CN_EMULATE
   (void)handle; (void)to_stream;
   return CN_OK;

@@ -176,8 +176,8 @@ extern "C" int cn_stem_fwd_rows(int N, int P) { return N * ((P + STEM_ROWS - 1) 
 // Q = Jp - 3 columns): cn_conv2d_fwd_bnstats on the pair image (R = 7, S = 4, stride (2, 1), no padding) as a halo
 // kernel; partial: cn_stem_fwd_rows(N, P) rows of 128 floats [sum | sum of squares] for cn_bn_fwd_train_partials (or the
 // fused stem pooling).  Same output bits as the tiled kernel.
-extern "C" int cn_stem_fwd(const void* xp, const void* wp, void* y, int N, int Hp, int Jp, int dtype, float* partial,
-                           int partial_rows, void* stream) {
+extern "C" cn_status cn_stem_fwd(const void* xp, const void* wp, void* y, int N, int Hp, int Jp, int dtype, float* partial,
+                                 int partial_rows, void* stream) {
   if (xp == nullptr || wp == nullptr || y == nullptr || partial == nullptr) { cn_set_error("stem_fwd: null operand"); return CN_EINVAL; }
   if (!cn_stem_fwd_ok(64, STEM_R, STEM_S2, Jp, dtype) || Hp < STEM_R || N <= 0) { cn_set_error("stem_fwd: unsupported shape"); return CN_ESHAPE; }
   StemParams p;
@@ -214,9 +214,6 @@ struct StemWgParams {
   int N, Hp, Jp, P, Q, nbands, nwork;
   FastDiv div_q;
 };
-
-int wg_launch_reduce(hipStream_t stream, const float* part, float* dw, int nsplit, int Co, int ntaps, int Ci, int Creal,
-                     float beta, float scale);   // wgrad.hip
 
 template <typename T>
 __global__ __launch_bounds__(512, 4) void stem_wgrad_kernel(StemWgParams p) {
@@ -336,8 +333,8 @@ extern "C" size_t cn_stem_wgrad_workspace(int N, int Hp) {
 // dwp [64][7][4][8] (fp32, the layout cn_wgrad_unpack_pairs takes) = beta*dwp + scale * the stem's weight gradient on the
 // pair image: cn_conv2d_wgrad(xp, dy, ...) with R = 7, S = 4, stride (2, 1) as a halo kernel.  Differs from the tiled
 // kernel by fp32 summation order only.
-extern "C" int cn_stem_wgrad(const void* xp, const void* dy, float* dwp, int N, int Hp, int Jp, int dtype, float beta,
-                             float scale, void* workspace, size_t ws_bytes, void* stream) {
+extern "C" cn_status cn_stem_wgrad(const void* xp, const void* dy, float* dwp, int N, int Hp, int Jp, int dtype, float beta,
+                                   float scale, void* workspace, size_t ws_bytes, void* stream) {
   if (xp == nullptr || dy == nullptr || dwp == nullptr) { cn_set_error("stem_wgrad: null operand"); return CN_EINVAL; }
   if (!cn_stem_wgrad_ok(64, STEM_R, STEM_S2, Jp, dtype) || Hp < STEM_R || N <= 0) { cn_set_error("stem_wgrad: unsupported shape"); return CN_ESHAPE; }
   StemWgParams p;

@@ -1048,20 +1048,20 @@ static int wg_conv2d_wgrad(const void* x, const void* dy, float* dw_krsc, int C_
                            int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
                            void* stream, const void* lazy_y, const float* lazy_coef);
 
-extern "C" int cn_conv2d_wgrad(const void* x, const void* dy, float* dw_krsc, int C_real, int N, int H, int W,
-                               int C, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
-                               int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
-                               void* stream) {
+extern "C" cn_status cn_conv2d_wgrad(const void* x, const void* dy, float* dw_krsc, int C_real, int N, int H, int W,
+                                     int C, int K, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w,
+                                     int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
+                                     void* stream) {
   return wg_conv2d_wgrad(x, dy, dw_krsc, C_real, N, H, W, C, K, R, S, stride_h, stride_w, pad_h, pad_w, dtype, beta,
                          scale, workspace, ws_bytes, stream, nullptr, nullptr);
 }
 
 // "Lazy dy" weight gradient (see cn_conv2d_dgrad_lazy): dy = c1*g + c2*y + c3 is formed on the operand load of the
 // register-staged kernel; same bits as cn_bn_bwd_partials(dy) + cn_conv2d_wgrad(dy) for the kernels it replaces.
-extern "C" int cn_conv2d_wgrad_lazy(const void* x, const void* g, const void* bn_y, const float* coef, float* dw_krsc,
-                                    int C_real, int N, int H, int W, int C, int K, int R, int S, int stride_h,
-                                    int stride_w, int pad_h, int pad_w, int dtype, float beta, float scale,
-                                    void* workspace, size_t ws_bytes, void* stream) {
+extern "C" cn_status cn_conv2d_wgrad_lazy(const void* x, const void* g, const void* bn_y, const float* coef, float* dw_krsc,
+                                          int C_real, int N, int H, int W, int C, int K, int R, int S, int stride_h,
+                                          int stride_w, int pad_h, int pad_w, int dtype, float beta, float scale,
+                                          void* workspace, size_t ws_bytes, void* stream) {
   if (g == nullptr || bn_y == nullptr || coef == nullptr) { cn_set_error("conv2d_wgrad_lazy: needs g, y and the coefficients"); return CN_EINVAL; }
   return wg_conv2d_wgrad(x, g, dw_krsc, C_real, N, H, W, C, K, R, S, stride_h, stride_w, pad_h, pad_w, dtype, beta, scale,
                          workspace, ws_bytes, stream, bn_y, coef);
@@ -1185,10 +1185,10 @@ extern "C" size_t cn_conv2d_bwd1x1_lazy_workspace(int N, int H, int W, int C, in
 // K output channels) for the upstream gradient dy = c1*g + c2*bn_y + c3 (coef = [c1 | c2 | c3], 3*K floats), formed
 // on load: cn_conv2d_dgrad_lazy + cn_conv2d_wgrad_lazy in one pass over g and bn_y.  dx has the bits of
 // cn_conv2d_dgrad_lazy; dw differs from cn_conv2d_wgrad_lazy by fp32 summation order only (other pixel ranges).
-extern "C" int cn_conv2d_bwd1x1_lazy(const void* x, const void* g, const void* bn_y, const float* coef,
-                                     const void* w_crsk, void* dx, float* dw_krsc, int N, int H, int W, int C, int K,
-                                     int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
-                                     void* stream) {
+extern "C" cn_status cn_conv2d_bwd1x1_lazy(const void* x, const void* g, const void* bn_y, const float* coef,
+                                           const void* w_crsk, void* dx, float* dw_krsc, int N, int H, int W, int C, int K,
+                                           int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
+                                           void* stream) {
   if (x == nullptr || g == nullptr || bn_y == nullptr || coef == nullptr || w_crsk == nullptr || dx == nullptr ||
       dw_krsc == nullptr) { cn_set_error("conv2d_bwd1x1_lazy: null operand"); return CN_EINVAL; }
   if (!cn_conv2d_bwd1x1_lazy_ok(C, K, dtype)) { cn_set_error("conv2d_bwd1x1_lazy: C=%d K=%d dtype %d is not an instantiated shape", C, K, dtype); return CN_ESHAPE; }

@@ -185,17 +185,16 @@ class ParamArena(object):
 
         def run():
             if self._qrows is not None:
-                _lib.check(L.cn_quantize_rows_multi(self.params.data_ptr(), self._qshadow.data_ptr(),
-                                                    self._qrows.data_ptr(), self._qrows.shape[0], st),
-                           'cn_quantize_rows_multi')
+                L.cn_quantize_rows_multi(self.params.data_ptr(), self._qshadow.data_ptr(),
+                                         self._qrows.data_ptr(), self._qrows.shape[0], st)
             if self._wdesc_reg is not None:
-                _lib.check(L.cn_weight_prep_tiled(src.data_ptr(), self.wbuf.data_ptr(),
-                                                  self._wdesc_reg.data_ptr(), self._wtiles.data_ptr(),
-                                                  self._wtiles.shape[0], code, st), 'cn_weight_prep_tiled')
+                L.cn_weight_prep_tiled(src.data_ptr(), self.wbuf.data_ptr(),
+                                       self._wdesc_reg.data_ptr(), self._wtiles.data_ptr(),
+                                       self._wtiles.shape[0], code, st)
             if self._wdesc is not None:
-                _lib.check(L.cn_weight_prep_multi(src.data_ptr(), self.wbuf.data_ptr(),
-                                                  self._wdesc.data_ptr(), self._wdesc.shape[0], self._wtotal, code,
-                                                  st), 'cn_weight_prep_multi')
+                L.cn_weight_prep_multi(src.data_ptr(), self.wbuf.data_ptr(),
+                                       self._wdesc.data_ptr(), self._wdesc.shape[0], self._wtotal, code,
+                                       st)
         ops.PROFILER.run('weight_prep', 2, 0.0, float(self._wbytes), run, self.device)
         self._wversion = self.version
 

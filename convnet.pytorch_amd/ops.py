@@ -17,7 +17,7 @@ import torch.distributed as dist
 from torch.autograd import Function
 
 from . import _lib, flags
-from ._lib import check, dtype_code, ptr, stream_of
+from ._lib import dtype_code, ptr, stream_of
 
 # ---------------------------------------------------------------------------------------------
 # workspaces: one grow-only scratch buffer per (device, tag, stream).  Kernels on one stream are ordered,
@@ -174,7 +174,7 @@ class SideStream(object):
         side = self.get(device)
         mark, self._mark = self._mark, None
         if mark is not None and dy is not None and dy.data_ptr() == mark[0]:
-            check(_L().cn_stream_wait_mark(mark[1], side.cuda_stream), 'cn_stream_wait_mark')   # dy's producer is done
+            _L().cn_stream_wait_mark(mark[1], side.cuda_stream)   # dy's producer is done
         else:
             self.fork(cur, side)
         with torch.cuda.stream(side):
@@ -183,7 +183,7 @@ class SideStream(object):
             # the operands stay referenced until the chain has waited for the side stream (join, once per step): the
             # caching allocator then needs no cross-stream bookkeeping for them.  record_stream would make it record an
             # event (with torch's default flags: a system-scope fence) on the side stream at every free and poll it
-            nbytes = sum(t.numel() * t.element_size() for t in held)
+            nbytes = sum(t.numel() * _esize(t) for t in held)
             self._held.append((held, nbytes))
             self._held_bytes += nbytes
             while len(self._held) > self.hold_max or (self._held_bytes > self.hold_max_bytes and len(self._held) > 1):
@@ -208,7 +208,7 @@ class SideStream(object):
 
     def fork(self, cur, side):
         """`side` waits for everything queued on `cur` so far (one device-scope event from the library's ring)."""
-        check(_L().cn_stream_fork(cur.cuda_stream, side.cuda_stream), 'cn_stream_fork')
+        _L().cn_stream_fork(cur.cuda_stream, side.cuda_stream)
 
     def join(self, device):
         """Make the current stream wait for everything queued on the side stream(s).  MANDATORY once per step for whoever
@@ -342,7 +342,18 @@ class _PendingStats(object):
     __slots__ = ('partial', 'rows', 'pivot')   # pivot: data_ptr of the running mean the sums are centred on (or None)
 
 
+def _stats_partial(want, K, device, rows_fn, *dims):
+    """(partial, rows) for a convolution that emits the statistics partials of its K output channels - rows_fn(*dims) is
+    the kernel's own row count - or (None, 0) when nobody wants them."""
+    if not want:
+        return None, 0
+    rows = rows_fn(*dims)
+    return torch.empty((rows, 2 * K), dtype=torch.float32, device=device), rows
+
+
 def _park_stats(y, partial, rows, pivot=None):
+    if partial is None:
+        return
     ps = _PendingStats()
     ps.partial, ps.rows = partial, rows
     ps.pivot = pivot.data_ptr() if pivot is not None else None
@@ -384,55 +395,46 @@ def conv2d_fwd(x, w_krsc, bias, K, R, S, stride, pad, out_f32=False, relu=False,
             and tuple(stride) == (1, 1) and tuple(pad) == (0, 0) \
             and _L().cn_conv1x1_stream_fwd_ok(C, K, dtype_code(x.dtype)):
         L = _L()
-        want = bn_stats
-        rows = L.cn_conv1x1_stream_fwd_rows(N, H, W, K) if want else 0
-        partial = torch.empty((rows, 2 * K), dtype=torch.float32, device=x.device) if want else None
+        partial, rows = _stats_partial(bn_stats, K, x.device, L.cn_conv1x1_stream_fwd_rows, N, H, W, K)
         PROFILER.run(_last_kernel(), 1, 2.0 * N * P * Q * K * C,
                      x.numel() * _esize(x) + y.numel() * _esize(y) + K * C * _esize(x),
-                     lambda: check(L.cn_conv1x1_stream_fwd(ptr(x), ptr(w_krsc), ptr(y), N, H, W, C, K, dtype_code(x.dtype),
-                                                           ptr(partial), rows, stream_of(x)), 'cn_conv1x1_stream_fwd'),
+                     lambda: L.cn_conv1x1_stream_fwd(ptr(x), ptr(w_krsc), ptr(y), N, H, W, C, K, dtype_code(x.dtype),
+                                                     ptr(partial), rows, stream_of(x)),
                      x.device, detail=_conv_detail('fwd', C, H, K, R, stride))
-        if want:
-            _park_stats(y, partial, rows, None)
+        _park_stats(y, partial, rows)
         return y
     if bias is None and not out_f32 and not relu and pivot is None and _halo3x3_ok(x, C, K, R, S, stride, pad):
         L = _L()
-        want = bn_stats
-        rows = L.cn_conv3x3_c64_rows(N, H) if want else 0
-        partial = torch.empty((rows, 2 * K), dtype=torch.float32, device=x.device) if want else None
+        partial, rows = _stats_partial(bn_stats, K, x.device, L.cn_conv3x3_c64_rows, N, H)
         PROFILER.run(_last_kernel(), 1, 2.0 * N * P * Q * K * C * R * S,
                      x.numel() * _esize(x) + y.numel() * _esize(y) + K * R * S * C * _esize(x),
-                     lambda: check(L.cn_conv3x3_c64(ptr(x), ptr(w_krsc), ptr(y), N, H, W, dtype_code(x.dtype), 0,
-                                                    ptr(partial), rows, stream_of(x)), 'cn_conv3x3_c64'),
+                     lambda: L.cn_conv3x3_c64(ptr(x), ptr(w_krsc), ptr(y), N, H, W, dtype_code(x.dtype), 0,
+                                              ptr(partial), rows, stream_of(x)),
                      x.device, detail=_conv_detail('fwd', C, H, K, R, stride))
-        if want:
-            _park_stats(y, partial, rows, None)
+        _park_stats(y, partial, rows)
         return y
     if bn_stats and not out_f32:
         L = _L()
-        rows = L.cn_conv2d_bnstats_rows(N * P * Q)
-        partial = torch.empty((rows, 2 * K), dtype=torch.float32, device=x.device)
+        partial, rows = _stats_partial(True, K, x.device, L.cn_conv2d_bnstats_rows, N * P * Q)
         PROFILER.run(_last_kernel(),
                      1, 2.0 * N * P * Q * K * C * R * S,
                      x.numel() * _esize(x) + y.numel() * _esize(y) + K * R * S * C * _esize(x) + partial.numel() * 4,
-                     (lambda: check(L.cn_conv2d_fwd_bnstats(ptr(x), ptr(w_krsc), ptr(y), ptr(bias), N, H, W, C, K, R, S,
-                                                            stride[0], stride[1], pad[0], pad[1], dtype_code(x.dtype),
-                                                            int(relu), ptr(partial), rows, stream_of(x)),
-                                    'cn_conv2d_fwd_bnstats')) if pivot is None else
-                     (lambda: check(L.cn_conv2d_fwd_bnstats_centered(ptr(x), ptr(w_krsc), ptr(y), ptr(bias), N, H, W, C,
-                                                                     K, R, S, stride[0], stride[1], pad[0], pad[1],
-                                                                     dtype_code(x.dtype), int(relu), ptr(partial), rows,
-                                                                     ptr(pivot), stream_of(x)),
-                                    'cn_conv2d_fwd_bnstats_centered')),
+                     (lambda: L.cn_conv2d_fwd_bnstats(ptr(x), ptr(w_krsc), ptr(y), ptr(bias), N, H, W, C, K, R, S,
+                                                      stride[0], stride[1], pad[0], pad[1], dtype_code(x.dtype),
+                                                      int(relu), ptr(partial), rows, stream_of(x))) if pivot is None else
+                     (lambda: L.cn_conv2d_fwd_bnstats_centered(ptr(x), ptr(w_krsc), ptr(y), ptr(bias), N, H, W, C,
+                                                               K, R, S, stride[0], stride[1], pad[0], pad[1],
+                                                               dtype_code(x.dtype), int(relu), ptr(partial), rows,
+                                                               ptr(pivot), stream_of(x))),
                      x.device, detail=_conv_detail('fwd', C, H, K, R, stride))
         _park_stats(y, partial, rows, pivot)
         return y
     PROFILER.run(_last_kernel(),
                  1, 2.0 * N * P * Q * K * C * R * S,
                  x.numel() * _esize(x) + y.numel() * _esize(y) + K * R * S * C * _esize(x),
-                 lambda: check(_L().cn_conv2d_fwd(ptr(x), ptr(w_krsc), ptr(y), ptr(bias), N, H, W, C, K, R, S,
-                                                  stride[0], stride[1], pad[0], pad[1], dtype_code(x.dtype),
-                                                  int(out_f32), int(relu), stream_of(x)), 'cn_conv2d_fwd'),
+                 lambda: _L().cn_conv2d_fwd(ptr(x), ptr(w_krsc), ptr(y), ptr(bias), N, H, W, C, K, R, S,
+                                            stride[0], stride[1], pad[0], pad[1], dtype_code(x.dtype),
+                                            int(out_f32), int(relu), stream_of(x)),
                  x.device, detail=_conv_detail('fwd', C, H, K, R, stride))
     return y
 
@@ -444,20 +446,16 @@ def conv2d_fwd_lazyz(lz, w_krsc, K, bn_stats=False, pivot=None):
     N, H, W, C = y3.shape
     out = torch.empty((N, H, W, K), dtype=y3.dtype, device=y3.device)
     L = _L()
-    partial, rows = None, 0
-    if bn_stats:
-        rows = L.cn_conv2d_bnstats_rows(N * H * W)
-        partial = torch.empty((rows, 2 * K), dtype=torch.float32, device=y3.device)
+    partial, rows = _stats_partial(bn_stats, K, y3.device, L.cn_conv2d_bnstats_rows, N * H * W)
     nb = y3.numel() * _esize(y3)
     PROFILER.run(_last_kernel(' [lazy z]'), 1, 2.0 * N * H * W * K * C,
                  3 * nb + (mask.numel() if mask is not None else 0) + out.numel() * _esize(out) + K * C * _esize(y3)
                  + (partial.numel() * 4 if partial is not None else 0),
-                 lambda: check(L.cn_conv2d_fwd_lazyz(ptr(y3), ptr(res), ptr(stats), ptr(res_stats), int(relu), ptr(z),
-                                                     ptr(mask), ptr(w_krsc), ptr(out), N, H, W, C, K, dtype_code(y3.dtype),
-                                                     ptr(partial), rows, ptr(pivot), stream_of(y3)), 'cn_conv2d_fwd_lazyz'),
+                 lambda: L.cn_conv2d_fwd_lazyz(ptr(y3), ptr(res), ptr(stats), ptr(res_stats), int(relu), ptr(z),
+                                               ptr(mask), ptr(w_krsc), ptr(out), N, H, W, C, K, dtype_code(y3.dtype),
+                                               ptr(partial), rows, ptr(pivot), stream_of(y3)),
                  y3.device, detail=_conv_detail('fwd', C, H, K, 1, (1, 1)))
-    if bn_stats:
-        _park_stats(out, partial, rows, pivot)
+    _park_stats(out, partial, rows, pivot)
     return out
 
 
@@ -493,29 +491,24 @@ def conv2d_fwd_lazya(la, w_krsc, K, bn_stats=False, kernel=(1, 1)):
     N, H, W, C = bn_y.shape
     L = _L()
     y = torch.empty((N, H, W, K), dtype=bn_y.dtype, device=bn_y.device)
-    want = bn_stats
     if tuple(kernel) == (3, 3):
-        rows = L.cn_conv3x3_c64_rows(N, H) if want else 0
-        partial = torch.empty((rows, 2 * K), dtype=torch.float32, device=bn_y.device) if want else None
+        partial, rows = _stats_partial(bn_stats, K, bn_y.device, L.cn_conv3x3_c64_rows, N, H)
         PROFILER.run(_last_kernel(' [lazy a]'), 1, 2.0 * N * H * W * K * C * 9,
                      2 * bn_y.numel() * _esize(bn_y) + y.numel() * _esize(y) + K * 9 * C * _esize(bn_y),
-                     lambda: check(L.cn_conv3x3_c64_lazya(ptr(bn_y), ptr(stats), int(relu), ptr(a), ptr(w_krsc), ptr(y),
-                                                          N, H, W, dtype_code(bn_y.dtype), ptr(partial), rows,
-                                                          stream_of(bn_y)), 'cn_conv3x3_c64_lazya'),
+                     lambda: L.cn_conv3x3_c64_lazya(ptr(bn_y), ptr(stats), int(relu), ptr(a), ptr(w_krsc), ptr(y),
+                                                    N, H, W, dtype_code(bn_y.dtype), ptr(partial), rows,
+                                                    stream_of(bn_y)),
                      bn_y.device, detail=_conv_detail('fwd', C, H, K, 3, (1, 1)))
-        if want:
-            _park_stats(y, partial, rows, None)
+        _park_stats(y, partial, rows)
         return y
-    rows = L.cn_conv1x1_stream_fwd_rows(N, H, W, K) if want else 0
-    partial = torch.empty((rows, 2 * K), dtype=torch.float32, device=bn_y.device) if want else None
+    partial, rows = _stats_partial(bn_stats, K, bn_y.device, L.cn_conv1x1_stream_fwd_rows, N, H, W, K)
     PROFILER.run(_last_kernel(' [lazy a]'), 1, 2.0 * N * H * W * K * C,
                  2 * bn_y.numel() * _esize(bn_y) + y.numel() * _esize(y) + K * C * _esize(bn_y),
-                 lambda: check(L.cn_conv1x1_stream_fwd_lazya(ptr(bn_y), ptr(stats), int(relu), ptr(a), ptr(w_krsc), ptr(y),
-                                                             N, H, W, C, K, dtype_code(bn_y.dtype), ptr(partial), rows,
-                                                             stream_of(bn_y)), 'cn_conv1x1_stream_fwd_lazya'),
+                 lambda: L.cn_conv1x1_stream_fwd_lazya(ptr(bn_y), ptr(stats), int(relu), ptr(a), ptr(w_krsc), ptr(y),
+                                                       N, H, W, C, K, dtype_code(bn_y.dtype), ptr(partial), rows,
+                                                       stream_of(bn_y)),
                  bn_y.device, detail=_conv_detail('fwd', C, H, K, 1, (1, 1)))
-    if want:
-        _park_stats(y, partial, rows, None)
+    _park_stats(y, partial, rows)
     return y
 
 
@@ -542,15 +535,15 @@ def conv2d_dgrad(dy, w_crsk, x_shape, K, R, S, stride, pad, addend=None, bn=None
         assert tuple(addend.shape) == (N, (H + 1) // 2, (W + 1) // 2, C), 'subsampled addend shape'
     if bn is None and addend is None and _halo3x3_ok(dy, K, C, R, S, stride, pad) and tuple(dy.shape[1:3]) == (H, W):
         PROFILER.run(name, 1, flops, nbytes,
-                     lambda: check(_L().cn_conv3x3_c64(ptr(dy), ptr(w_crsk), ptr(dx), N, H, W, dtype_code(dy.dtype), 1, None,
-                                                       0, stream_of(dy)), 'cn_conv3x3_c64'),
+                     lambda: _L().cn_conv3x3_c64(ptr(dy), ptr(w_crsk), ptr(dx), N, H, W, dtype_code(dy.dtype), 1, None,
+                                                 0, stream_of(dy)),
                      dy.device, detail=detail)
         return dx
     if bn is None:
         PROFILER.run(name, stride[0] * stride[1], flops, nbytes,
-                     lambda: check(_L().cn_conv2d_dgrad_sa(ptr(dy), ptr(w_crsk), ptr(dx), ptr(addend), int(addend_sub), N, H,
-                                                           W, C, K, R, S, stride[0], stride[1], pad[0], pad[1],
-                                                           dtype_code(dy.dtype), 0, stream_of(dy)), 'cn_conv2d_dgrad'),
+                     lambda: _L().cn_conv2d_dgrad_sa(ptr(dy), ptr(w_crsk), ptr(dx), ptr(addend), int(addend_sub), N, H,
+                                                     W, C, K, R, S, stride[0], stride[1], pad[0], pad[1],
+                                                     dtype_code(dy.dtype), 0, stream_of(dy)),
                      dy.device, detail=detail)
         return dx
     bn_y, bn_mask, bn_stats, bn_relu = bn
@@ -560,23 +553,37 @@ def conv2d_dgrad(dy, w_crsk, x_shape, K, R, S, stride, pad, addend=None, bn=None
         rows = L.cn_conv2d_dgrad_junction_rows_k(N, H, W, C, K)
         partial = torch.empty((rows, 2 * C), dtype=torch.float32, device=dy.device)
         PROFILER.run(_last_kernel(), 1, flops, nbytes + dx.numel() * _esize(dx) + partial.numel() * 4,
-                     lambda: check(L.cn_conv2d_dgrad_junction(ptr(dy), ptr(w_crsk), ptr(dx), ptr(addend), int(addend_sub), N,
-                                                              H, W, C, K, dtype_code(dy.dtype), ptr(bn_y), ptr(bn_mask),
-                                                              ptr(bn_stats), ptr(partial), rows, stream_of(dy)),
-                                   'cn_conv2d_dgrad_junction'),
+                     lambda: L.cn_conv2d_dgrad_junction(ptr(dy), ptr(w_crsk), ptr(dx), ptr(addend), int(addend_sub), N,
+                                                        H, W, C, K, dtype_code(dy.dtype), ptr(bn_y), ptr(bn_mask),
+                                                        ptr(bn_stats), ptr(partial), rows, stream_of(dy)),
                      dy.device, detail=detail)
         COUNTERS['jdgrad'] = COUNTERS.get('jdgrad', 0) + 1
         return dx, partial, rows
     rows = L.cn_conv2d_dgrad_bnbwd_rows(N, H, W, C, stride[0], stride[1])
     partial = torch.empty((rows, 2 * C), dtype=torch.float32, device=dy.device)
     PROFILER.run(name, stride[0] * stride[1], flops, nbytes + dx.numel() * _esize(dx) + partial.numel() * 4,
-                 lambda: check(L.cn_conv2d_dgrad_bnbwd_sa(ptr(dy), ptr(w_crsk), ptr(dx), ptr(addend), int(addend_sub), N, H,
-                                                          W, C, K, R, S, stride[0], stride[1], pad[0], pad[1],
-                                                          dtype_code(dy.dtype), ptr(bn_y), ptr(bn_mask), ptr(bn_stats),
-                                                          int(bn_relu), ptr(partial), rows, stream_of(dy)),
-                               'cn_conv2d_dgrad_bnbwd'),
+                 lambda: L.cn_conv2d_dgrad_bnbwd_sa(ptr(dy), ptr(w_crsk), ptr(dx), ptr(addend), int(addend_sub), N, H,
+                                                    W, C, K, R, S, stride[0], stride[1], pad[0], pad[1],
+                                                    dtype_code(dy.dtype), ptr(bn_y), ptr(bn_mask), ptr(bn_stats),
+                                                    int(bn_relu), ptr(partial), rows, stream_of(dy)),
                  dy.device, detail=detail)
     return dx, partial, rows
+
+
+def _wgrad_two_phase(call, device, flops, bytes_partial, bytes_reduce, detail, suffix=''):
+    """A weight-gradient entry point whose call() makes two launches: partial products, then the fixed-order reduction of
+    the splits.  Profiled, the two are timed separately - measurement-only knob "wgrad_phase" - so each is reported under
+    its own kernel name."""
+    if not (PROFILER.enabled and device.type == 'cuda'):
+        return call()
+    L = _L()
+    L.cn_set_option(b'wgrad_phase', 1)
+    try:
+        PROFILER.run(_last_kernel(suffix), 1, flops, bytes_partial, call, device, detail=detail)
+        L.cn_set_option(b'wgrad_phase', 2)
+        PROFILER.run('wgrad_reduce_kernel', 1, 0.0, bytes_reduce, call, device, detail=detail + ' [reduce]')
+    finally:
+        L.cn_set_option(b'wgrad_phase', 0)
 
 
 def conv2d_wgrad(x, dy, dw_krsc, c_real, K, R, S, stride, pad, beta=1.0, scale=1.0, tag='main'):
@@ -586,26 +593,13 @@ def conv2d_wgrad(x, dy, dw_krsc, c_real, K, R, S, stride, pad, beta=1.0, scale=1
     L = _L()
     need = L.cn_conv2d_wgrad_workspace(N, H, W, C, K, R, S, stride[0], stride[1], pad[0], pad[1], code)
     ws = workspace(need, x.device, tag)
+
     def call():
-        check(L.cn_conv2d_wgrad(ptr(x), ptr(dy), ptr(dw_krsc), c_real, N, H, W, C, K, R, S, stride[0], stride[1],
-                                pad[0], pad[1], code, beta, scale, ptr(ws), ws.numel() * 4, stream_of(x)),
-              'cn_conv2d_wgrad')
-    if not (PROFILER.enabled and x.is_cuda):
-        return call()
-    # profiled: the call's two launches (partial products, then the fixed-order reduction of the splits) are timed
-    # separately - measurement-only knob "wgrad_phase" - so each is reported under its own kernel name
-    flops = 2.0 * dy.numel() * C * R * S
-    part_bytes = float(need)
-    detail = _conv_detail('wgrad', C, H, K, R, stride)
-    L.cn_set_option(b'wgrad_phase', 1)
-    try:
-        PROFILER.run(_last_kernel(), 1, flops, x.numel() * _esize(x) + dy.numel() * _esize(dy) + part_bytes, call,
-                     x.device, detail=detail)
-        L.cn_set_option(b'wgrad_phase', 2)
-        PROFILER.run('wgrad_reduce_kernel', 1, 0.0, part_bytes + K * R * S * c_real * 4, call, x.device,
-                     detail=detail + ' [reduce]')
-    finally:
-        L.cn_set_option(b'wgrad_phase', 0)
+        L.cn_conv2d_wgrad(ptr(x), ptr(dy), ptr(dw_krsc), c_real, N, H, W, C, K, R, S, stride[0], stride[1],
+                          pad[0], pad[1], code, beta, scale, ptr(ws), ws.numel() * 4, stream_of(x))
+    _wgrad_two_phase(call, x.device, 2.0 * dy.numel() * C * R * S,
+                     x.numel() * _esize(x) + dy.numel() * _esize(dy) + float(need), float(need) + K * R * S * c_real * 4,
+                     _conv_detail('wgrad', C, H, K, R, stride))
 
 
 def conv2d_dgrad_lazy(g, bn_y, coef, w_crsk, x_shape, K, R, S, stride, pad):
@@ -616,16 +610,15 @@ def conv2d_dgrad_lazy(g, bn_y, coef, w_crsk, x_shape, K, R, S, stride, pad):
             and _L().cn_conv2d_dgrad_lazy_stream_ok(C, K, dtype_code(g.dtype)):
         PROFILER.run(_last_kernel(' [lazy dy]'), 1, 2.0 * g.numel() * C,
                      2 * g.numel() * _esize(g) + dx.numel() * _esize(dx) + K * C * _esize(g),
-                     lambda: check(_L().cn_conv2d_dgrad_lazy_stream(ptr(g), ptr(bn_y), ptr(coef), ptr(w_crsk), ptr(dx), N, H, W,
-                                                                    C, K, dtype_code(g.dtype), stream_of(g)),
-                                   'cn_conv2d_dgrad_lazy_stream'),
+                     lambda: _L().cn_conv2d_dgrad_lazy_stream(ptr(g), ptr(bn_y), ptr(coef), ptr(w_crsk), ptr(dx), N, H, W,
+                                                              C, K, dtype_code(g.dtype), stream_of(g)),
                      g.device, detail=_conv_detail('dgrad', C, H, K, R, stride))
         return dx
     PROFILER.run(_last_kernel(' [lazy dy]'), stride[0] * stride[1], 2.0 * g.numel() * C * R * S,
                  2 * g.numel() * _esize(g) + dx.numel() * _esize(dx) + K * R * S * C * _esize(g),
-                 lambda: check(_L().cn_conv2d_dgrad_lazy(ptr(g), ptr(bn_y), ptr(coef), ptr(w_crsk), ptr(dx), N, H, W, C, K,
-                                                         R, S, stride[0], stride[1], pad[0], pad[1], dtype_code(g.dtype),
-                                                         stream_of(g)), 'cn_conv2d_dgrad_lazy'),
+                 lambda: _L().cn_conv2d_dgrad_lazy(ptr(g), ptr(bn_y), ptr(coef), ptr(w_crsk), ptr(dx), N, H, W, C, K,
+                                                   R, S, stride[0], stride[1], pad[0], pad[1], dtype_code(g.dtype),
+                                                   stream_of(g)),
                  g.device, detail=_conv_detail('dgrad', C, H, K, R, stride))
     return dx
 
@@ -639,9 +632,9 @@ def conv2d_wgrad_lazy(x, g, bn_y, coef, dw_krsc, c_real, K, R, S, stride, pad, b
     ws = workspace(need, x.device, tag)
     PROFILER.run(_last_kernel(' [lazy dy] (+wgrad_reduce)'), 2, 2.0 * g.numel() * C * R * S,
                  x.numel() * _esize(x) + 2 * g.numel() * _esize(g) + float(need),
-                 lambda: check(L.cn_conv2d_wgrad_lazy(ptr(x), ptr(g), ptr(bn_y), ptr(coef), ptr(dw_krsc), c_real, N, H, W, C,
-                                                      K, R, S, stride[0], stride[1], pad[0], pad[1], code, beta, scale,
-                                                      ptr(ws), ws.numel() * 4, stream_of(x)), 'cn_conv2d_wgrad_lazy'),
+                 lambda: L.cn_conv2d_wgrad_lazy(ptr(x), ptr(g), ptr(bn_y), ptr(coef), ptr(dw_krsc), c_real, N, H, W, C,
+                                                K, R, S, stride[0], stride[1], pad[0], pad[1], code, beta, scale,
+                                                ptr(ws), ws.numel() * 4, stream_of(x)),
                  x.device, detail=_conv_detail('wgrad', C, H, K, R, stride))
 
 
@@ -656,21 +649,10 @@ def conv2d_bwd1x1_lazy(x, g, bn_y, coef, w_crsk, dw_krsc, K, beta=1.0, scale=1.0
     dx = torch.empty_like(x)
 
     def call():
-        check(L.cn_conv2d_bwd1x1_lazy(ptr(x), ptr(g), ptr(bn_y), ptr(coef), ptr(w_crsk), ptr(dx), ptr(dw_krsc), N, H, W, C,
-                                      K, code, beta, scale, ptr(ws), ws.numel() * 4, stream_of(x)), 'cn_conv2d_bwd1x1_lazy')
-    if not (PROFILER.enabled and x.is_cuda):
-        call()
-        return dx
-    flops = 4.0 * g.numel() * C
-    detail = _conv_detail('dgrad+wgrad', C, H, K, 1, (1, 1))
-    L.cn_set_option(b'wgrad_phase', 1)
-    try:
-        PROFILER.run(_last_kernel(' [lazy dy]'), 1, flops, 2 * g.numel() * _esize(g) + 2 * x.numel() * _esize(x)
-                     + float(need), call, x.device, detail=detail)
-        L.cn_set_option(b'wgrad_phase', 2)
-        PROFILER.run('wgrad_reduce_kernel', 1, 0.0, float(need) + K * C * 4, call, x.device, detail=detail + ' [reduce]')
-    finally:
-        L.cn_set_option(b'wgrad_phase', 0)
+        L.cn_conv2d_bwd1x1_lazy(ptr(x), ptr(g), ptr(bn_y), ptr(coef), ptr(w_crsk), ptr(dx), ptr(dw_krsc), N, H, W, C,
+                                K, code, beta, scale, ptr(ws), ws.numel() * 4, stream_of(x))
+    _wgrad_two_phase(call, x.device, 4.0 * g.numel() * C, 2 * g.numel() * _esize(g) + 2 * x.numel() * _esize(x) + float(need),
+                     float(need) + K * C * 4, _conv_detail('dgrad+wgrad', C, H, K, 1, (1, 1)), suffix=' [lazy dy]')
     return dx
 
 
@@ -688,8 +670,8 @@ def gconv2d_fwd(x, w, K, groups, stride):
     cg = C // groups
     PROFILER.run(_last_kernel(), 1, 2.0 * N * P * Q * K * 9 * cg,
                  x.numel() * _esize(x) + y.numel() * _esize(y) + K * 9 * cg * _esize(x),
-                 lambda: check(_L().cn_gconv2d_fwd(ptr(x), ptr(w), ptr(y), N, H, W, C, K, groups, stride,
-                                                   dtype_code(x.dtype), stream_of(x)), 'cn_gconv2d_fwd'),
+                 lambda: _L().cn_gconv2d_fwd(ptr(x), ptr(w), ptr(y), N, H, W, C, K, groups, stride,
+                                             dtype_code(x.dtype), stream_of(x)),
                  x.device, detail=_conv_detail('gfwd', C, H, K, 3, (stride, stride)))
     return y
 
@@ -699,8 +681,8 @@ def gconv2d_dgrad(dy, w, x_shape, K, groups, stride):
     dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
     PROFILER.run(_last_kernel(), 1, 2.0 * dy.numel() * 9 * (C // groups),
                  dy.numel() * _esize(dy) + dx.numel() * _esize(dx) + K * 9 * (C // groups) * _esize(dy),
-                 lambda: check(_L().cn_gconv2d_dgrad(ptr(dy), ptr(w), ptr(dx), N, H, W, C, K, groups, stride,
-                                                     dtype_code(dy.dtype), stream_of(dy)), 'cn_gconv2d_dgrad'),
+                 lambda: _L().cn_gconv2d_dgrad(ptr(dy), ptr(w), ptr(dx), N, H, W, C, K, groups, stride,
+                                               dtype_code(dy.dtype), stream_of(dy)),
                  dy.device, detail=_conv_detail('gdgrad', C, H, K, 3, (stride, stride)))
     return dx
 
@@ -714,24 +696,22 @@ def gconv2d_wgrad(x, dy, dw, K, groups, stride, beta=1.0, scale=1.0, tag='main')
     ws = workspace(need, x.device, tag)
     PROFILER.run(_last_kernel(), 2, 2.0 * dy.numel() * 9 * (C // groups),
                  x.numel() * _esize(x) + dy.numel() * _esize(dy) + 2.0 * need + K * 9 * (C // groups) * 4,
-                 lambda: check(L.cn_gconv2d_wgrad(ptr(x), ptr(dy), ptr(dw), N, H, W, C, K, groups, stride, code, beta,
-                                                  scale, ptr(ws), ws.numel() * 4, stream_of(x)), 'cn_gconv2d_wgrad'),
+                 lambda: L.cn_gconv2d_wgrad(ptr(x), ptr(dy), ptr(dw), N, H, W, C, K, groups, stride, code, beta,
+                                            scale, ptr(ws), ws.numel() * 4, stream_of(x)),
                  x.device, detail=_conv_detail('gwgrad', C, H, K, 3, (stride, stride)))
 
 
 def weight_prep(w_master_krsc, w_krsc, w_crsk, Co, taps, c_real, c_pad):
     PROFILER.run('weight_prep', 1, 0.0, Co * taps * c_real * 4 + Co * taps * c_pad * _esize(w_krsc) * (2 if w_crsk is not None else 1),
-                 lambda: check(_L().cn_weight_prep(ptr(w_master_krsc), ptr(w_krsc), ptr(w_crsk), Co, taps, c_real,
-                                                   c_pad, dtype_code(w_krsc.dtype), stream_of(w_krsc)),
-                               'cn_weight_prep'), w_krsc.device)
+                 lambda: _L().cn_weight_prep(ptr(w_master_krsc), ptr(w_krsc), ptr(w_crsk), Co, taps, c_real,
+                                             c_pad, dtype_code(w_krsc.dtype), stream_of(w_krsc)), w_krsc.device)
 
 
 def colsum(x2d, out, beta=1.0, scale=1.0):
     M, C = x2d.shape
     L = _L()
     ws = workspace(L.cn_colsum_workspace(C), x2d.device, 'colsum')
-    check(L.cn_colsum(ptr(x2d), ptr(out), M, C, dtype_code(x2d.dtype), beta, scale, ptr(ws), stream_of(x2d)),
-          'cn_colsum')
+    L.cn_colsum(ptr(x2d), ptr(out), M, C, dtype_code(x2d.dtype), beta, scale, ptr(ws), stream_of(x2d))
 
 
 def nchw_to_nhwc(x_nchw, dtype, c_pad=None):
@@ -745,8 +725,8 @@ def nchw_to_nhwc(x_nchw, dtype, c_pad=None):
         raise _lib.ConvNetHipError('nchw_to_nhwc expects float32 input, got %s' % x_nchw.dtype)
     y = torch.empty((N, H, W, c_pad), dtype=dtype, device=x_nchw.device)
     PROFILER.run('nchw_to_nhwc', 1, 0.0, x_nchw.numel() * 4 + y.numel() * _esize(y),
-                 lambda: check(_L().cn_nchw_to_nhwc(ptr(x_nchw), ptr(y), N, C, H, W, c_pad, dtype_code(dtype),
-                                                    stream_of(x_nchw)), 'cn_nchw_to_nhwc'), x_nchw.device)
+                 lambda: _L().cn_nchw_to_nhwc(ptr(x_nchw), ptr(y), N, C, H, W, c_pad, dtype_code(dtype),
+                                              stream_of(x_nchw)), x_nchw.device)
     return y
 
 
@@ -769,8 +749,8 @@ def resize_crops(batch):
     tmp = torch.empty(rows * S * C, dtype=torch.uint8, device=px.device)
     out = torch.empty((B, S, S, C), dtype=torch.uint8, device=px.device)
     PROFILER.run('resize_u8_crops', 2, 0.0, px.numel() + 2 * tmp.numel() + out.numel(),
-                 lambda: check(_L().cn_resize_u8_crops(ptr(px), ptr(meta), ptr(tables), ptr(row_owner), ptr(row_off), ptr(tmp),
-                                                       ptr(out), B, rows, S, C, stream_of(px)), 'cn_resize_u8_crops'), px.device)
+                 lambda: _L().cn_resize_u8_crops(ptr(px), ptr(meta), ptr(tables), ptr(row_owner), ptr(row_off), ptr(tmp),
+                                                 ptr(out), B, rows, S, C, stream_of(px)), px.device)
     return out
 
 
@@ -785,8 +765,7 @@ def u8_nhwc_to_nchw(x_u8, lut):
         raise _lib.ConvNetHipError('u8_nhwc_to_nchw: lut %s for %d channels' % (tuple(lut.shape), C))
     y = torch.empty((N, C, H, W), dtype=torch.float32, device=x_u8.device)
     PROFILER.run('u8_nhwc_to_nchw', 1, 0.0, x_u8.numel() + y.numel() * 4,
-                 lambda: check(_L().cn_u8_nhwc_to_nchw_lut(ptr(x_u8), ptr(y), N, H, W, C, ptr(lut), stream_of(x_u8)),
-                               'cn_u8_nhwc_to_nchw_lut'), x_u8.device)
+                 lambda: _L().cn_u8_nhwc_to_nchw_lut(ptr(x_u8), ptr(y), N, H, W, C, ptr(lut), stream_of(x_u8)), x_u8.device)
     return y
 
 
@@ -798,8 +777,8 @@ def nchw_to_pairs(x_nchw, pad):
         raise _lib.ConvNetHipError('nchw_to_pairs expects float32 input, got %s' % x_nchw.dtype)
     y = torch.empty((N, H + 2 * pad[0], (W + 2 * pad[1]) // 2, 8), dtype=torch.bfloat16, device=x_nchw.device)
     PROFILER.run('nchw_to_pairs', 1, 0.0, x_nchw.numel() * 4 + y.numel() * 2,
-                 lambda: check(_L().cn_nchw_to_pairs(ptr(x_nchw), ptr(y), N, C, H, W, pad[0], pad[1],
-                                                     stream_of(x_nchw)), 'cn_nchw_to_pairs'), x_nchw.device)
+                 lambda: _L().cn_nchw_to_pairs(ptr(x_nchw), ptr(y), N, C, H, W, pad[0], pad[1],
+                                               stream_of(x_nchw)), x_nchw.device)
     return y
 
 
@@ -807,26 +786,25 @@ def nhwc_to_nchw(x_nhwc, C=None):
     N, H, W, Cp = x_nhwc.shape
     C = C or Cp
     y = torch.empty((N, C, H, W), dtype=torch.float32, device=x_nhwc.device)
-    check(_L().cn_nhwc_to_nchw(ptr(x_nhwc), ptr(y), N, C, H, W, Cp, dtype_code(x_nhwc.dtype), stream_of(x_nhwc)),
-          'cn_nhwc_to_nchw')
+    _L().cn_nhwc_to_nchw(ptr(x_nhwc), ptr(y), N, C, H, W, Cp, dtype_code(x_nhwc.dtype), stream_of(x_nhwc))
     return y
 
 
 def add_(a, b):
     PROFILER.run('eltwise_add', 1, 0.0, 3 * a.numel() * _esize(a),
-                 lambda: check(_L().cn_eltwise(0, ptr(a), ptr(b), None, a.numel(), dtype_code(a.dtype),
-                                               stream_of(a)), 'cn_eltwise'), a.device)
+                 lambda: _L().cn_eltwise(0, ptr(a), ptr(b), None, a.numel(), dtype_code(a.dtype),
+                                         stream_of(a)), a.device)
     return a
 
 
 def cast_from_f32(x, dtype):
     y = torch.empty(x.shape, dtype=dtype, device=x.device)
-    check(_L().cn_cast_from_f32(ptr(x), ptr(y), x.numel(), dtype_code(dtype), stream_of(x)), 'cn_cast_from_f32')
+    _L().cn_cast_from_f32(ptr(x), ptr(y), x.numel(), dtype_code(dtype), stream_of(x))
     return y
 
 
 def fill_f32_(x, v=0.0):
-    check(_L().cn_fill_f32(ptr(x), x.numel(), float(v), stream_of(x)), 'cn_fill_f32')
+    _L().cn_fill_f32(ptr(x), x.numel(), float(v), stream_of(x))
     return x
 
 
@@ -878,6 +856,18 @@ def _zero_like_placeholder(x):
 def _is_zero_placeholder(t):
     z = _ZEROS.get((t.device, t.dtype))
     return z is not None and t.data_ptr() == z.data_ptr() and t.dim() > 0 and all(st == 0 for st in t.stride())
+
+
+def _submit_wgrad(mod, run, held, dy):
+    """A layer's weight gradient run(tag): on the side stream when that is in use - it waits for `dy`'s producer, and
+    `held` (the operands; held[0] tells the device) plus whatever scratch run() returns stay referenced until the join -
+    else right here; then the gradient is reported ready."""
+    x = held[0]
+    if SIDE.active(x):
+        SIDE.submit(x.device, lambda: held + (run('side') or ()), mod._notify_grad_ready, dy)
+    else:
+        run('main')
+        mod._notify_grad_ready()
 
 
 class Conv2dFunction(Function):
@@ -941,16 +931,9 @@ class Conv2dFunction(Function):
                 if holder is not None:
                     holder.dres, holder.sub, holder.fused = dx, 1, False
                 return dx, None, None, None
-            if SIDE.active(x):
-                def launch():
-                    conv2d_wgrad_lazy(x, g, bn_y, coef, mod.grad_view('weight'), mod.in_channels, mod.out_channels, R, S,
-                                      mod.stride, mod.padding, tag='side')
-                    return (x, g, bn_y, coef)
-                SIDE.submit(x.device, launch, mod._notify_grad_ready, coef)
-            else:
-                conv2d_wgrad_lazy(x, g, bn_y, coef, mod.grad_view('weight'), mod.in_channels, mod.out_channels, R, S,
-                                  mod.stride, mod.padding)
-                mod._notify_grad_ready()
+            _submit_wgrad(mod, lambda tag: conv2d_wgrad_lazy(x, g, bn_y, coef, mod.grad_view('weight'), mod.in_channels,
+                                                             mod.out_channels, R, S, mod.stride, mod.padding, tag=tag),
+                          (x, g, bn_y, coef), coef)
             if not ctx.needs_input_grad[0]:
                 return None, None, None, None
             holder = getattr(mod, '_res_holder', None)
@@ -972,17 +955,10 @@ class Conv2dFunction(Function):
             dy = cast_from_f32(dy, x.dtype)
         if ctx.has_bias:
             colsum(dy.view(-1, mod.out_channels), mod.grad_view('bias'))
+
         def submit_wgrad():
-            if SIDE.active(x):
-                def launch():
-                    conv2d_wgrad(x, dy, mod.grad_view('weight'), mod.in_channels, mod.out_channels, R, S, mod.stride,
-                                 mod.padding, tag='side')
-                    return (x, dy)
-                SIDE.submit(x.device, launch, mod._notify_grad_ready, dy)
-            else:
-                conv2d_wgrad(x, dy, mod.grad_view('weight'), mod.in_channels, mod.out_channels, R, S, mod.stride,
-                             mod.padding)
-                mod._notify_grad_ready()
+            _submit_wgrad(mod, lambda tag: conv2d_wgrad(x, dy, mod.grad_view('weight'), mod.in_channels, mod.out_channels,
+                                                        R, S, mod.stride, mod.padding, tag=tag), (x, dy), dy)
 
         def dgrad_part():
             dx = None
@@ -1063,14 +1039,7 @@ class GroupedConv2dFunction(Function):
         K, g, st = mod.out_channels, mod.groups, mod.stride[0]
 
         def submit_wgrad():
-            if SIDE.active(x):
-                def launch():
-                    gconv2d_wgrad(x, dy, mod.grad_view('weight'), K, g, st, tag='side')
-                    return (x, dy)
-                SIDE.submit(x.device, launch, mod._notify_grad_ready, dy)
-            else:
-                gconv2d_wgrad(x, dy, mod.grad_view('weight'), K, g, st)
-                mod._notify_grad_ready()
+            _submit_wgrad(mod, lambda tag: gconv2d_wgrad(x, dy, mod.grad_view('weight'), K, g, st, tag=tag), (x, dy), dy)
 
         if not DGRAD_FIRST:
             submit_wgrad()
@@ -1113,22 +1082,21 @@ class StemPairConvFunction(Function):
         S2 = (S + 1) // 2
         L = _L()
         wp = torch.empty(K * R * S2 * 8, dtype=torch.bfloat16, device=x_pairs.device)
-        check(L.cn_weight_prep_pairs(ptr(mod.master_view('weight')), ptr(wp), K, R, S, mod.in_channels,
-                                     stream_of(x_pairs)), 'cn_weight_prep_pairs')
+        L.cn_weight_prep_pairs(ptr(mod.master_view('weight')), ptr(wp), K, R, S, mod.in_channels,
+                               stream_of(x_pairs))
         want_stats = FUSE_BN_STATS and mod.training and getattr(mod, 'feeds_batchnorm', False)
         N_, Hp_, Jp_, _ = x_pairs.shape
         if STEM_HALO and want_stats and stats_pivot(mod) is None and mod.stride[0] == 2 and x_pairs.dtype == torch.bfloat16 \
                 and L.cn_stem_fwd_ok(K, R, S2, Jp_, dtype_code(x_pairs.dtype)):
             P_, Q_ = (Hp_ - R) // 2 + 1, Jp_ - S2 + 1
             y = torch.empty((N_, P_, Q_, K), dtype=x_pairs.dtype, device=x_pairs.device)
-            rows = L.cn_stem_fwd_rows(N_, P_)
-            partial = torch.empty((rows, 2 * K), dtype=torch.float32, device=x_pairs.device)
+            partial, rows = _stats_partial(True, K, x_pairs.device, L.cn_stem_fwd_rows, N_, P_)
             PROFILER.run(_last_kernel(), 1, 2.0 * N_ * P_ * Q_ * K * 8 * R * S2,
                          x_pairs.numel() * 2 + y.numel() * 2 + wp.numel() * 2 + partial.numel() * 4,
-                         lambda: check(L.cn_stem_fwd(ptr(x_pairs), ptr(wp), ptr(y), N_, Hp_, Jp_, dtype_code(x_pairs.dtype),
-                                                     ptr(partial), rows, stream_of(x_pairs)), 'cn_stem_fwd'),
+                         lambda: L.cn_stem_fwd(ptr(x_pairs), ptr(wp), ptr(y), N_, Hp_, Jp_, dtype_code(x_pairs.dtype),
+                                               ptr(partial), rows, stream_of(x_pairs)),
                          x_pairs.device, detail=_conv_detail('fwd', 8, Hp_, K, R, (2, 1)))
-            _park_stats(y, partial, rows, None)
+            _park_stats(y, partial, rows)
         else:
             y = conv2d_fwd(x_pairs, wp, None, K, R, S2, (mod.stride[0], 1), (0, 0), bn_stats=want_stats,
                            pivot=stats_pivot(mod))
@@ -1154,32 +1122,17 @@ class StemPairConvFunction(Function):
                 ws = workspace(need, x.device, tag)
 
                 def call():
-                    check(L.cn_stem_wgrad(ptr(x), ptr(dy), ptr(tmp), N_, Hp_, Jp_, code, 0.0, 1.0, ptr(ws), ws.numel() * 4,
-                                          stream_of(x)), 'cn_stem_wgrad')
-                if PROFILER.enabled and x.is_cuda:
-                    detail = _conv_detail('wgrad', 8, Hp_, K, R, (2, 1))
-                    L.cn_set_option(b'wgrad_phase', 1)
-                    try:
-                        PROFILER.run(_last_kernel(), 1, 2.0 * dy.numel() * 8 * R * S2,
-                                     x.numel() * 2 + dy.numel() * 2 + float(need), call, x.device, detail=detail)
-                        L.cn_set_option(b'wgrad_phase', 2)
-                        PROFILER.run('wgrad_reduce_kernel', 1, 0.0, float(need) + tmp.numel() * 4, call, x.device,
-                                     detail=detail + ' [reduce]')
-                    finally:
-                        L.cn_set_option(b'wgrad_phase', 0)
-                else:
-                    call()
+                    L.cn_stem_wgrad(ptr(x), ptr(dy), ptr(tmp), N_, Hp_, Jp_, code, 0.0, 1.0, ptr(ws), ws.numel() * 4,
+                                    stream_of(x))
+                _wgrad_two_phase(call, x.device, 2.0 * dy.numel() * 8 * R * S2, x.numel() * 2 + dy.numel() * 2 + float(need),
+                                 float(need) + tmp.numel() * 4, _conv_detail('wgrad', 8, Hp_, K, R, (2, 1)))
             else:
                 conv2d_wgrad(x, dy, tmp, 8, K, R, S2, (mod.stride[0], 1), (0, 0), beta=0.0, tag=tag)
-            check(L.cn_wgrad_unpack_pairs(ptr(tmp), ptr(mod.grad_view('weight')), K, R, S, mod.in_channels, 1.0,
-                                          stream_of(x)), 'cn_wgrad_unpack_pairs')
-            return tmp
+            L.cn_wgrad_unpack_pairs(ptr(tmp), ptr(mod.grad_view('weight')), K, R, S, mod.in_channels, 1.0,
+                                    stream_of(x))
+            return (tmp,)
 
-        if SIDE.active(x):
-            SIDE.submit(x.device, lambda: (x, dy, run('side')), mod._notify_grad_ready, dy)
-        else:
-            run('main')
-            mod._notify_grad_ready()
+        _submit_wgrad(mod, run, (x, dy), dy)
         return None, None, None
 
 
@@ -1195,6 +1148,14 @@ def _lazy_dy_ok(bn_mod, y):
     if y.shape[-1] > 512 or y.dtype not in (torch.bfloat16, torch.float16, torch.float32):
         return False
     return y.numel() * _esize(y) >= LAZY_DY_MIN_MB * 2 ** 20
+
+
+def _running_ptrs(mod):
+    """Pointers to (running_mean, running_var, num_batches_tracked) for the kernels that update them; NULLs for a
+    BatchNorm that tracks no running statistics."""
+    if not mod.track_running_stats:
+        return None, None, None
+    return ptr(mod.running_mean), ptr(mod.running_var), ptr(mod.num_batches_tracked)
 
 
 class BatchNormActFunction(Function):
@@ -1250,39 +1211,32 @@ class BatchNormActFunction(Function):
             # Equal per-rank batch sizes (DistributedSampler pads to that) give the global row count.
             group, world = sync
             sums = torch.empty(2 * C, dtype=torch.float64, device=y.device)
-            check(L.cn_bn_local_sums(ptr(y), M, C, code, ptr(ps.partial) if ps is not None else None,
-                                     ps.rows if ps is not None else 0, ptr(sums), ptr(ws), ws.numel() * 4,
-                                     stream_of(y)), 'cn_bn_local_sums')
+            L.cn_bn_local_sums(ptr(y), M, C, code, ptr(ps.partial) if ps is not None else None,
+                               ps.rows if ps is not None else 0, ptr(sums), ptr(ws), ws.numel() * 4,
+                               stream_of(y))
             _sync_all_reduce(sums, group, world)
-            check(L.cn_bn_fwd_train_sums(ptr(y), ptr(residual), ptr(z), ptr(mask), ptr(gamma), ptr(beta),
-                                         ptr(mod.running_mean) if track else None,
-                                         ptr(mod.running_var) if track else None,
-                                         ptr(mod.num_batches_tracked) if track else None, momentum, mod.eps,
-                                         ptr(stats), M, C, int(relu), code, ptr(sums), M * world, stream_of(y)),
-                  'cn_bn_fwd_train_sums')
+            L.cn_bn_fwd_train_sums(ptr(y), ptr(residual), ptr(z), ptr(mask), ptr(gamma), ptr(beta),
+                                   *_running_ptrs(mod), momentum, mod.eps, ptr(stats), M, C, int(relu), code, ptr(sums),
+                                   M * world, stream_of(y))
         elif ps is not None:   # statistics came out of the producing convolution's epilogue: no pass over y
             PROFILER.run('bn_finalize+bn_apply (stats from conv epilogue)' if zk is not None
                          else 'bn_finalize (stats from conv epilogue; applied by the junction)',
                          (2 if ps.rows <= 512 else 3) - (0 if zk is not None else 1), 0.0,
                          (nb * (3 if residual is not None else 2) + (mask.numel() if mask is not None else 0)
                           if zk is not None else 0) + ps.partial.numel() * 4,
-                         lambda: check((L.cn_bn_fwd_train_partials if ps.pivot is None
-                                        else L.cn_bn_fwd_train_partials_centered)(
-                             ptr(y), ptr(residual) if zk is not None else None, ptr(zk), ptr(mask) if zk is not None else None, ptr(gamma), ptr(beta),
-                             ptr(mod.running_mean) if track else None, ptr(mod.running_var) if track else None,
-                             ptr(mod.num_batches_tracked) if track else None, momentum, mod.eps, ptr(stats), M, C,
-                             int(relu), code, ptr(ps.partial), ps.rows, ptr(ws), ws.numel() * 4, stream_of(y)),
-                             'cn_bn_fwd_train_partials'),
+                         lambda: (L.cn_bn_fwd_train_partials if ps.pivot is None else L.cn_bn_fwd_train_partials_centered)(
+                             ptr(y), ptr(residual) if zk is not None else None, ptr(zk), ptr(mask) if zk is not None else None,
+                             ptr(gamma), ptr(beta), *_running_ptrs(mod), momentum, mod.eps, ptr(stats), M, C, int(relu), code,
+                             ptr(ps.partial), ps.rows, ptr(ws), ws.numel() * 4, stream_of(y)),
                          y.device)
         else:
             PROFILER.run('bn_stats+bn_finalize+bn_apply' if zk is not None else 'bn_stats+bn_finalize', 3 if zk is not None else 2, 0.0,
                          nb * (4 if residual is not None else 3) + (mask.numel() if mask is not None else 0)
                          if zk is not None else nb,
-                         lambda: check(L.cn_bn_fwd_train(
-                             ptr(y), ptr(residual) if zk is not None else None, ptr(zk), ptr(mask) if zk is not None else None, ptr(gamma), ptr(beta),
-                             ptr(mod.running_mean) if track else None, ptr(mod.running_var) if track else None,
-                             ptr(mod.num_batches_tracked) if track else None, momentum, mod.eps, ptr(stats), M, C,
-                             int(relu), code, ptr(ws), ws.numel() * 4, stream_of(y)), 'cn_bn_fwd_train'),
+                         lambda: L.cn_bn_fwd_train(
+                             ptr(y), ptr(residual) if zk is not None else None, ptr(zk), ptr(mask) if zk is not None else None,
+                             ptr(gamma), ptr(beta), *_running_ptrs(mod), momentum, mod.eps, ptr(stats), M, C, int(relu), code,
+                             ptr(ws), ws.numel() * 4, stream_of(y)),
                          y.device)
         if lazyz:
             cons.__dict__['_lazy_z'] = (z.data_ptr(), y, residual.contiguous(), stats, dual, z, mask, relu)
@@ -1291,8 +1245,8 @@ class BatchNormActFunction(Function):
         elif dual is not None:    # both BatchNorms finalised: one apply pass reads y and the shortcut's raw input
             PROFILER.run('bn_apply (junction + projection-shortcut BatchNorm)', 1, 0.0,
                          nb * 3 + (mask.numel() if mask is not None else 0),
-                         lambda: check(L.cn_bn_apply_dual(ptr(y), ptr(residual), ptr(z), ptr(mask), ptr(stats), ptr(dual),
-                                                          M, C, int(relu), code, stream_of(y)), 'cn_bn_apply_dual'),
+                         lambda: L.cn_bn_apply_dual(ptr(y), ptr(residual), ptr(z), ptr(mask), ptr(stats), ptr(dual),
+                                                    M, C, int(relu), code, stream_of(y)),
                          y.device)
             COUNTERS['bn_fwd_dual'] = COUNTERS.get('bn_fwd_dual', 0) + 1
         ctx.mod = mod
@@ -1332,20 +1286,19 @@ class BatchNormActFunction(Function):
             group, world = ctx.sync
             COUNTERS['bn_bwd_fused' if fused_in else 'bn_bwd_plain'] += 1
             local = torch.empty(2 * C, dtype=torch.float64, device=y.device)
-            check(L.cn_bn_bwd_local_sums(ptr(dz), ptr(y), ptr(zmask), ptr(stats), M, C, int(ctx.relu), code,
-                                         ptr(pp[2]) if fused_in else None, pp[3] if fused_in else 0, ptr(local),
-                                         ptr(ws), ws.numel() * 4, stream_of(y)), 'cn_bn_bwd_local_sums')
+            L.cn_bn_bwd_local_sums(ptr(dz), ptr(y), ptr(zmask), ptr(stats), M, C, int(ctx.relu), code,
+                                   ptr(pp[2]) if fused_in else None, pp[3] if fused_in else 0, ptr(local),
+                                   ptr(ws), ws.numel() * 4, stream_of(y))
             glob = local.clone()
             _sync_all_reduce(glob, group, world)
             if fused_in:
                 dres = dz if want_res else None
             else:
                 dres = torch.empty_like(y) if want_res else None
-            check(L.cn_bn_bwd_sums(ptr(dz), ptr(y), ptr(zmask), ptr(mod.weight), ptr(stats), ptr(dy),
-                                   None if fused_in else ptr(dres), ptr(mod.grad_view('weight')),
-                                   ptr(mod.grad_view('bias')), 1.0, 1.0, ptr(coef), M, C, int(ctx.relu),
-                                   int(fused_in), code, ptr(local), ptr(glob), M * world, stream_of(y)),
-                  'cn_bn_bwd_sums')
+            L.cn_bn_bwd_sums(ptr(dz), ptr(y), ptr(zmask), ptr(mod.weight), ptr(stats), ptr(dy),
+                             None if fused_in else ptr(dres), ptr(mod.grad_view('weight')),
+                             ptr(mod.grad_view('bias')), 1.0, 1.0, ptr(coef), M, C, int(ctx.relu),
+                             int(fused_in), code, ptr(local), ptr(glob), M * world, stream_of(y))
         elif fused_in and _lazy_dy_ok(mod, y):
             # ... and the apply pass is left to the consumers: finalize only, dy = c1*g + c2*y + c3 is formed on the
             # operand loads of the producing convolution's dgrad / wgrad (see LAZY_DY)
@@ -1355,11 +1308,10 @@ class BatchNormActFunction(Function):
             dres = dz if want_res else None
             with SIDE.mark(coef):
                 PROFILER.run('bn_bwd_finalize (lazy dy)', 1 if rows <= 512 else 2, 0.0, partial.numel() * 4,
-                             lambda: check(L.cn_bn_bwd_partials(ptr(dz), ptr(y), ptr(mod.weight), ptr(stats), None,
-                                                                ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')),
-                                                                1.0, 1.0, ptr(coef), M, C, code, ptr(partial), rows,
-                                                                ptr(ws), ws.numel() * 4, stream_of(y)),
-                                           'cn_bn_bwd_partials'),
+                             lambda: L.cn_bn_bwd_partials(ptr(dz), ptr(y), ptr(mod.weight), ptr(stats), None,
+                                                          ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')),
+                                                          1.0, 1.0, ptr(coef), M, C, code, ptr(partial), rows,
+                                                          ptr(ws), ws.numel() * 4, stream_of(y)),
                              y.device)
             mod.producer_conv._lazy_dy = (dz, y, coef)
             dy = _zero_like_placeholder(y)
@@ -1371,11 +1323,10 @@ class BatchNormActFunction(Function):
             with SIDE.mark(dy):
                 PROFILER.run('bn_bwd_finalize+bn_bwd_apply (reduce in dgrad epilogue)', 2 if rows <= 512 else 3, 0.0,
                              nb * 3 + partial.numel() * 4,
-                             lambda: check(L.cn_bn_bwd_partials(ptr(dz), ptr(y), ptr(mod.weight), ptr(stats), ptr(dy),
-                                                                ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')),
-                                                                1.0, 1.0, ptr(coef), M, C, code, ptr(partial), rows,
-                                                                ptr(ws), ws.numel() * 4, stream_of(y)),
-                                           'cn_bn_bwd_partials'),
+                             lambda: L.cn_bn_bwd_partials(ptr(dz), ptr(y), ptr(mod.weight), ptr(stats), ptr(dy),
+                                                          ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')),
+                                                          1.0, 1.0, ptr(coef), M, C, code, ptr(partial), rows,
+                                                          ptr(ws), ws.numel() * 4, stream_of(y)),
                              y.device)
         elif not ctx.relu and not want_res and zmask is None and _lazy_dy_ok(mod, y):
             # a BatchNorm with no activation behind it (the projection shortcut's): reduce + finalize, apply left to the
@@ -1385,10 +1336,10 @@ class BatchNormActFunction(Function):
             dres = None
             with SIDE.mark(coef):
                 PROFILER.run('bn_bwd_reduce+bn_bwd_finalize (lazy dy)', 2, 0.0, nb * 2,
-                             lambda: check(L.cn_bn_bwd(ptr(dz), ptr(y), None, ptr(mod.weight), ptr(stats), None,
-                                                       None, ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')),
-                                                       1.0, 1.0, ptr(coef), M, C, 0, code, ptr(ws),
-                                                       ws.numel() * 4, stream_of(y)), 'cn_bn_bwd'),
+                             lambda: L.cn_bn_bwd(ptr(dz), ptr(y), None, ptr(mod.weight), ptr(stats), None,
+                                                 None, ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')),
+                                                 1.0, 1.0, ptr(coef), M, C, 0, code, ptr(ws),
+                                                 ws.numel() * 4, stream_of(y)),
                              y.device)
             mod.producer_conv._lazy_dy = (dz, y, coef)
             dy = _zero_like_placeholder(y)
@@ -1398,10 +1349,10 @@ class BatchNormActFunction(Function):
             with SIDE.mark(dy):
                 PROFILER.run('bn_bwd_reduce+bn_bwd_finalize+bn_bwd_apply', 3, 0.0,
                              nb * (5 + (1 if dres is not None else 0)) + (2 * zmask.numel() if zmask is not None else 0),
-                             lambda: check(L.cn_bn_bwd(ptr(dz), ptr(y), ptr(zmask), ptr(mod.weight), ptr(stats), ptr(dy),
-                                                       ptr(dres), ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')),
-                                                       1.0, 1.0, ptr(coef), M, C, int(ctx.relu), code, ptr(ws),
-                                                       ws.numel() * 4, stream_of(y)), 'cn_bn_bwd'),
+                             lambda: L.cn_bn_bwd(ptr(dz), ptr(y), ptr(zmask), ptr(mod.weight), ptr(stats), ptr(dy),
+                                                 ptr(dres), ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')),
+                                                 1.0, 1.0, ptr(coef), M, C, int(ctx.relu), code, ptr(ws),
+                                                 ws.numel() * 4, stream_of(y)),
                              y.device)
         mod._notify_grad_ready()
         holder = getattr(mod, '_res_holder', None)
@@ -1416,9 +1367,9 @@ def batch_norm_infer(y, residual, mod, relu):
     N, H, W, C = y.shape
     z = torch.empty_like(y)
     coeffs = torch.empty(2 * C, dtype=torch.float32, device=y.device)
-    check(_L().cn_bn_fwd_infer(ptr(y), ptr(residual), ptr(z), ptr(mod.weight), ptr(mod.bias),
-                               ptr(mod.running_mean), ptr(mod.running_var), mod.eps, ptr(coeffs), N * H * W, C,
-                               int(relu), dtype_code(y.dtype), stream_of(y)), 'cn_bn_fwd_infer')
+    _L().cn_bn_fwd_infer(ptr(y), ptr(residual), ptr(z), ptr(mod.weight), ptr(mod.bias),
+                         ptr(mod.running_mean), ptr(mod.running_var), mod.eps, ptr(coeffs), N * H * W, C,
+                         int(relu), dtype_code(y.dtype), stream_of(y))
     return z
 
 
@@ -1430,8 +1381,8 @@ class MaxPool2dFunction(Function):
         y = torch.empty((N, P, Q, C), dtype=x.dtype, device=x.device)
         idx = torch.empty((N, P, Q, C), dtype=torch.uint8, device=x.device)
         PROFILER.run('maxpool_fwd', 1, 0.0, x.numel() * _esize(x) + y.numel() * (_esize(y) + 1),
-                     lambda: check(_L().cn_maxpool_fwd(ptr(x), ptr(y), ptr(idx), N, H, W, C, k, stride, pad,
-                                                       dtype_code(x.dtype), stream_of(x)), 'cn_maxpool_fwd'),
+                     lambda: _L().cn_maxpool_fwd(ptr(x), ptr(y), ptr(idx), N, H, W, C, k, stride, pad,
+                                                 dtype_code(x.dtype), stream_of(x)),
                      x.device)
         ctx.cfg = (N, H, W, C, k, stride, pad)
         ctx.save_for_backward(idx)
@@ -1444,8 +1395,8 @@ class MaxPool2dFunction(Function):
         dy = dy.contiguous()
         dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
         PROFILER.run('maxpool_bwd', 1, 0.0, dx.numel() * _esize(dx) + dy.numel() * (_esize(dy) + 1),
-                     lambda: check(_L().cn_maxpool_bwd(ptr(dy), ptr(idx), ptr(dx), N, H, W, C, k, stride, pad,
-                                                       dtype_code(dy.dtype), stream_of(dy)), 'cn_maxpool_bwd'),
+                     lambda: _L().cn_maxpool_bwd(ptr(dy), ptr(idx), ptr(dx), N, H, W, C, k, stride, pad,
+                                                 dtype_code(dy.dtype), stream_of(dy)),
                      dy.device)
         return dx, None, None, None
 
@@ -1466,9 +1417,7 @@ class BnReluMaxPoolFunction(Function):
         stats = torch.empty(4 * C, dtype=torch.float32, device=y.device)
         momentum = mod.effective_momentum()
         track = mod.track_running_stats
-        rm = ptr(mod.running_mean) if track else None
-        rv = ptr(mod.running_var) if track else None
-        nbt = ptr(mod.num_batches_tracked) if track else None
+        rm, rv, nbt = _running_ptrs(mod)
         ps = take_pending_stats(y)
         if ps is not None and ps.pivot is not None and not (track and ps.pivot == mod.running_mean.data_ptr()):
             ps = None
@@ -1482,20 +1431,17 @@ class BnReluMaxPoolFunction(Function):
         def run():
             if ps is not None:
                 fn = L.cn_bn_fwd_train_partials if ps.pivot is None else L.cn_bn_fwd_train_partials_centered
-                check(fn(ptr(y), None, None, None, ptr(gamma), ptr(beta), rm, rv, nbt, momentum,
-                         mod.eps, ptr(stats), M, C, 1, code, ptr(ps.partial), ps.rows, ptr(ws),
-                         ws.numel() * 4, stream_of(y)), 'cn_bn_fwd_train_partials')
+                fn(ptr(y), None, None, None, ptr(gamma), ptr(beta), rm, rv, nbt, momentum, mod.eps, ptr(stats), M, C, 1, code,
+                   ptr(ps.partial), ps.rows, ptr(ws), ws.numel() * 4, stream_of(y))
             else:
-                check(L.cn_bn_fwd_train(ptr(y), None, None, None, ptr(gamma), ptr(beta), rm, rv, nbt, momentum, mod.eps,
-                                        ptr(stats), M, C, 1, code, ptr(ws), ws.numel() * 4, stream_of(y)),
-                      'cn_bn_fwd_train')
+                L.cn_bn_fwd_train(ptr(y), None, None, None, ptr(gamma), ptr(beta), rm, rv, nbt, momentum, mod.eps,
+                                  ptr(stats), M, C, 1, code, ptr(ws), ws.numel() * 4, stream_of(y))
             if xmax is not None:
-                check(L.cn_maxpool_fwd_bnrelu_xmax(ptr(y), ptr(stats[2 * C:3 * C]), ptr(stats[3 * C:]), ptr(out), ptr(idx),
-                                                   ptr(xmax), N, H, W, C, k, stride, pad, code, stream_of(y)),
-                      'cn_maxpool_fwd_bnrelu_xmax')
+                L.cn_maxpool_fwd_bnrelu_xmax(ptr(y), ptr(stats[2 * C:3 * C]), ptr(stats[3 * C:]), ptr(out), ptr(idx),
+                                             ptr(xmax), N, H, W, C, k, stride, pad, code, stream_of(y))
             else:
-                check(L.cn_maxpool_fwd_bnrelu(ptr(y), ptr(stats[2 * C:3 * C]), ptr(stats[3 * C:]), ptr(out), ptr(idx), N, H,
-                                              W, C, k, stride, pad, code, stream_of(y)), 'cn_maxpool_fwd_bnrelu')
+                L.cn_maxpool_fwd_bnrelu(ptr(y), ptr(stats[2 * C:3 * C]), ptr(stats[3 * C:]), ptr(out), ptr(idx), N, H,
+                                        W, C, k, stride, pad, code, stream_of(y))
         PROFILER.run('bn_finalize+maxpool_fwd_bnrelu (stem)', 3, 0.0,
                      y.numel() * _esize(y) * (1 if ps is not None else 2)
                      + out.numel() * (_esize(out) * (2 if xmax is not None else 1) + 1), run, y.device)
@@ -1525,16 +1471,16 @@ class BnReluMaxPoolFunction(Function):
             PROFILER.run('bn_bwd_maxpool (stem)', 3, 0.0,
                          (y.numel() * _esize(y) * 3 + dpool.numel() * (_esize(dpool) + 1) * 2) if xmax is None else
                          (y.numel() * _esize(y) * 2 + dpool.numel() * (3 * _esize(dpool) + 1)),
-                         (lambda: check(L.cn_bn_bwd_maxpool(ptr(dpool), ptr(idx), ptr(y), ptr(mod.weight), ptr(stats), ptr(dy),
-                                                            ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')), 1.0, 1.0,
-                                                            ptr(coef), N, H, W, C, k, stride, pad, code, ptr(ws),
-                                                            ws.numel() * 4, stream_of(y)), 'cn_bn_bwd_maxpool'))
+                         (lambda: L.cn_bn_bwd_maxpool(ptr(dpool), ptr(idx), ptr(y), ptr(mod.weight), ptr(stats), ptr(dy),
+                                                      ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')), 1.0, 1.0,
+                                                      ptr(coef), N, H, W, C, k, stride, pad, code, ptr(ws),
+                                                      ws.numel() * 4, stream_of(y)))
                          if xmax is None else
-                         (lambda: check(L.cn_bn_bwd_maxpool_xmax(ptr(dpool), ptr(idx), ptr(y), ptr(xmax), ptr(mod.weight),
-                                                                 ptr(stats), ptr(dy), ptr(mod.grad_view('weight')),
-                                                                 ptr(mod.grad_view('bias')), 1.0, 1.0, ptr(coef), N, H, W, C,
-                                                                 k, stride, pad, code, ptr(ws), ws.numel() * 4,
-                                                                 stream_of(y)), 'cn_bn_bwd_maxpool_xmax')),
+                         (lambda: L.cn_bn_bwd_maxpool_xmax(ptr(dpool), ptr(idx), ptr(y), ptr(xmax), ptr(mod.weight),
+                                                           ptr(stats), ptr(dy), ptr(mod.grad_view('weight')),
+                                                           ptr(mod.grad_view('bias')), 1.0, 1.0, ptr(coef), N, H, W, C,
+                                                           k, stride, pad, code, ptr(ws), ws.numel() * 4,
+                                                           stream_of(y))),
                          y.device)
         mod._notify_grad_ready()
         return dy, None, None, None, None, None, None
@@ -1545,8 +1491,7 @@ class GlobalAvgPoolFunction(Function):
     def forward(ctx, x):
         N, H, W, C = x.shape
         y = torch.empty((N, 1, 1, C), dtype=x.dtype, device=x.device)
-        check(_L().cn_avgpool_fwd(ptr(x), ptr(y), N, H * W, C, dtype_code(x.dtype), stream_of(x)),
-              'cn_avgpool_fwd')
+        _L().cn_avgpool_fwd(ptr(x), ptr(y), N, H * W, C, dtype_code(x.dtype), stream_of(x))
         ctx.shape = (N, H, W, C)
         return y
 
@@ -1555,8 +1500,7 @@ class GlobalAvgPoolFunction(Function):
         N, H, W, C = ctx.shape
         dy = dy.contiguous()
         dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
-        check(_L().cn_avgpool_bwd(ptr(dy), ptr(dx), N, H * W, C, dtype_code(dy.dtype), stream_of(dy)),
-              'cn_avgpool_bwd')
+        _L().cn_avgpool_bwd(ptr(dy), ptr(dx), N, H * W, C, dtype_code(dy.dtype), stream_of(dy))
         return dx
 
 
@@ -1564,7 +1508,7 @@ class ReLUFunction(Function):
     @staticmethod
     def forward(ctx, x):
         z = torch.empty_like(x)
-        check(_L().cn_eltwise(1, ptr(z), ptr(x), None, x.numel(), dtype_code(x.dtype), stream_of(x)), 'cn_eltwise')
+        _L().cn_eltwise(1, ptr(z), ptr(x), None, x.numel(), dtype_code(x.dtype), stream_of(x))
         ctx.save_for_backward(z)
         return z
 
@@ -1573,8 +1517,7 @@ class ReLUFunction(Function):
         (z,) = ctx.saved_tensors
         dz = dz.contiguous()
         dx = torch.empty_like(dz)
-        check(_L().cn_eltwise(2, ptr(dx), ptr(dz), ptr(z), dz.numel(), dtype_code(dz.dtype), stream_of(dz)),
-              'cn_eltwise')
+        _L().cn_eltwise(2, ptr(dx), ptr(dz), ptr(z), dz.numel(), dtype_code(dz.dtype), stream_of(dz))
         return dx
 
 
@@ -1584,7 +1527,7 @@ class DropoutFunction(Function):
     @staticmethod
     def forward(ctx, x, mask):
         z = torch.empty_like(x)
-        check(_L().cn_eltwise(3, ptr(z), ptr(x), ptr(mask), x.numel(), dtype_code(x.dtype), stream_of(x)), 'cn_eltwise')
+        _L().cn_eltwise(3, ptr(z), ptr(x), ptr(mask), x.numel(), dtype_code(x.dtype), stream_of(x))
         ctx.save_for_backward(mask)
         return z
 
@@ -1593,8 +1536,7 @@ class DropoutFunction(Function):
         (mask,) = ctx.saved_tensors
         dz = dz.contiguous()
         dx = torch.empty_like(dz)
-        check(_L().cn_eltwise(3, ptr(dx), ptr(dz), ptr(mask), dz.numel(), dtype_code(dz.dtype), stream_of(dz)),
-              'cn_eltwise')
+        _L().cn_eltwise(3, ptr(dx), ptr(dz), ptr(mask), dz.numel(), dtype_code(dz.dtype), stream_of(dz))
         return dx, None
 
 
@@ -1606,8 +1548,8 @@ class SmallLinearFunction(Function):
         B, C = x2d.shape
         K = mod.out_channels
         y = torch.empty((B, K), dtype=torch.float32, device=x2d.device)
-        check(_L().cn_small_linear(0, ptr(x2d), ptr(mod.master_view('weight')), ptr(bias), ptr(y), None, None, B, C,
-                                   K, dtype_code(x2d.dtype), stream_of(x2d)), 'cn_small_linear')
+        _L().cn_small_linear(0, ptr(x2d), ptr(mod.master_view('weight')), ptr(bias), ptr(y), None, None, B, C,
+                             K, dtype_code(x2d.dtype), stream_of(x2d))
         ctx.mod = mod
         ctx.save_for_backward(x2d)
         return y
@@ -1622,14 +1564,14 @@ class SmallLinearFunction(Function):
         L = _L()
         code = dtype_code(x2d.dtype)
         db = mod.grad_view('bias') if mod.bias is not None else None
-        check(L.cn_small_linear(2, ptr(x2d), None, None, ptr(dy), ptr(mod.grad_view('weight')), ptr(db), B, C, K, code,
-                                stream_of(x2d)), 'cn_small_linear')
+        L.cn_small_linear(2, ptr(x2d), None, None, ptr(dy), ptr(mod.grad_view('weight')), ptr(db), B, C, K, code,
+                          stream_of(x2d))
         mod._notify_grad_ready()
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x2d)
-            check(L.cn_small_linear(1, ptr(dy), ptr(mod.master_view('weight')), None, ptr(dx), None, None, B, C, K,
-                                    code, stream_of(x2d)), 'cn_small_linear')
+            L.cn_small_linear(1, ptr(dy), ptr(mod.master_view('weight')), None, ptr(dx), None, None, B, C, K,
+                              code, stream_of(x2d))
         return dx, None, None, None
 
 
@@ -1694,9 +1636,8 @@ class SoftmaxCrossEntropyFunction(Function):
         target = target.contiguous()
         row = torch.empty(3 * B, dtype=torch.float32, device=logits.device)
         step_out = torch.empty(3, dtype=torch.float32, device=logits.device)
-        check(_L().cn_softmax_ce(ptr(logits), ptr(target), None, _lib.F32, ptr(row), ptr(step_out),
-                                 ptr(crit.meters), B, K, 1.0, None, crit.smooth_eps, stream_of(logits)),
-              'cn_softmax_ce')
+        _L().cn_softmax_ce(ptr(logits), ptr(target), None, _lib.F32, ptr(row), ptr(step_out),
+                           ptr(crit.meters), B, K, 1.0, None, crit.smooth_eps, stream_of(logits))
         crit.last_step = step_out
         ctx.crit = crit
         ctx.save_for_backward(logits, target, row)
@@ -1708,8 +1649,8 @@ class SoftmaxCrossEntropyFunction(Function):
         B, K = logits.shape
         dlogits = torch.empty_like(logits)
         go = go.contiguous().to(torch.float32)
-        check(_L().cn_softmax_ce(ptr(logits), ptr(target), ptr(dlogits), _lib.F32, ptr(row), None, None, B, K,
-                                 1.0 / B, ptr(go), ctx.crit.smooth_eps, stream_of(logits)), 'cn_softmax_ce')
+        _L().cn_softmax_ce(ptr(logits), ptr(target), ptr(dlogits), _lib.F32, ptr(row), None, None, B, K,
+                           1.0 / B, ptr(go), ctx.crit.smooth_eps, stream_of(logits))
         return dlogits, None, None
 
 
@@ -1719,6 +1660,6 @@ def accuracy_counts(logits, target):
     logits = logits.contiguous().float()
     row = torch.empty(3 * B, dtype=torch.float32, device=logits.device)
     out = torch.empty(3, dtype=torch.float32, device=logits.device)
-    check(_L().cn_softmax_ce(ptr(logits), ptr(target.contiguous()), None, _lib.F32, ptr(row), ptr(out), None, B, K,
-                             1.0, None, 0.0, stream_of(logits)), 'cn_softmax_ce')
+    _L().cn_softmax_ce(ptr(logits), ptr(target.contiguous()), None, _lib.F32, ptr(row), ptr(out), None, B, K,
+                       1.0, None, 0.0, stream_of(logits))
     return out

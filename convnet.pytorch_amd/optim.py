@@ -17,7 +17,7 @@ from copy import deepcopy
 import torch
 
 from . import _lib, engine, ops
-from ._lib import check, ptr, stream_of
+from ._lib import ptr, stream_of
 
 
 def eval_func(f, x):
@@ -189,11 +189,10 @@ class OptimRegime(Regime):
         for start, end, wd in self._runs:
             n = end - start
             ops.PROFILER.run('sgd_momentum', 1, 0.0, 20.0 * n,
-                             lambda: check(L.cn_sgd_momentum(ptr(a.params[start:]), ptr(a.grads[start:]),
-                                                             ptr(self.momentum_buf[start:]), n, lr, mu, float(wd),
-                                                             float(self.grad_scale), ptr(self.clip_coef),
-                                                             ptr(self.hyper_dev), stream_of(a.params)),
-                                               'cn_sgd_momentum'),
+                             lambda: L.cn_sgd_momentum(ptr(a.params[start:]), ptr(a.grads[start:]),
+                                                       ptr(self.momentum_buf[start:]), n, lr, mu, float(wd),
+                                                       float(self.grad_scale), ptr(self.clip_coef),
+                                                       ptr(self.hyper_dev), stream_of(a.params)),
                              a.device)
         a.bump_version()
 

@@ -373,10 +373,10 @@ class Trainer(object):
             clip_coef = None
             if self.grad_clip > 0:
                 a = self.arena
-                check(_lib.load().cn_grad_norm_clip(ptr(a.grads), a.grads.numel(), gscale, float(self.grad_clip),
-                                                    ptr(self._norm_out), ptr(self._meters[4:]),
-                                                    float(inputs_batch.size(0)), ptr(self._norm_ws),
-                                                    stream_of(a.grads)), 'cn_grad_norm_clip')
+                _lib.load().cn_grad_norm_clip(ptr(a.grads), a.grads.numel(), gscale, float(self.grad_clip),
+                                              ptr(self._norm_out), ptr(self._meters[4:]),
+                                              float(inputs_batch.size(0)), ptr(self._norm_ws),
+                                              stream_of(a.grads))
                 grad = self._norm_out[0]
                 clip_coef = self._norm_out[1:2]
             self.optimizer.grad_scale = gscale

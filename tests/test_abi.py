@@ -71,3 +71,59 @@ def test_ops_refuse_host_tensors_on_the_product_library():
         pytest.skip('emulator bound in this process')
     with pytest.raises(ca._lib.ConvNetHipError):
         ca.ops.nchw_to_nhwc(torch.zeros(1, 3, 4, 4), torch.float32)
+
+
+# ---- the binding is parsed from the header (_lib.parse_header) -------------------------------------------------------
+
+def test_parser_covers_the_header():
+    import convnet_amd as ca
+    txt = open(os.path.join(ROOT, 'include', 'convnet_hip.h')).read()
+    assert sorted(ca._lib.parse_header(txt)) == _header_symbols()
+    assert sorted(ca._lib._SIGNATURES) == _header_symbols()
+
+
+def test_parsed_signatures_match_hand_written_ones():
+    """Three declarations that span the type map, against literals copied from the hand-written table the parser
+    replaced (size_t + floats; unsigned long long + long long; a string return)."""
+    import convnet_amd as ca
+    c_p, c_i, c_f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    c_ll, c_sz, c_ull = ctypes.c_longlong, ctypes.c_size_t, ctypes.c_ulonglong
+    want = {
+        'cn_conv2d_wgrad': (c_i, [c_p, c_p, c_p, c_i] + [c_i] * 11 + [c_i, c_f, c_f, c_p, c_sz, c_p]),
+        'cn_quantize': (c_i, [c_p, c_p, c_ll, c_i, c_p, c_p, c_i, c_p, c_i, c_ull, c_p]),
+        'cn_build_info': (ctypes.c_char_p, []),
+    }
+    for name, (res, args) in want.items():
+        got = ca._lib._SIGNATURES[name]
+        assert (got[0], list(got[1])) == (res, args), name
+    # the one string PARAMETER of the ABI stays a string, the opaque 128-byte id a plain pointer
+    assert ca._lib._SIGNATURES['cn_set_option'][1] == [ctypes.c_char_p, c_i]
+    assert ca._lib._SIGNATURES['cn_comm_init'][1] == [c_p, c_p, c_i, c_i]
+
+
+@pytest.mark.parametrize('text', [
+    'int cn_good(int a);\nint cn_bad(double v);',                 # a parameter type outside the ABI's vocabulary
+    'struct cn_thing cn_bad(void);',                              # ... a return type
+    'int cn_good(int a);\nint cn_bad(int (*callback)(int));',     # a declaration the pattern cannot account for
+    'int cn_good(int a);\nint cn_bad(int a)\n',                   # ... (no terminating semicolon)
+])
+def test_parser_fails_loudly(text):
+    import convnet_amd as ca
+    with pytest.raises(ca._lib.ConvNetHipError):
+        ca._lib.parse_header(text)
+    assert list(ca._lib.parse_header('int cn_good(int a);')) == ['cn_good']
+
+
+def test_status_return_raises_under_its_own_name():
+    """A cn_status entry point raises from the binding itself, named after the symbol that failed: addend_sub = 3 is
+    refused before any launch (no pointer is touched)."""
+    import convnet_amd as ca
+    L = ca._lib.load()
+    with pytest.raises(ca._lib.ConvNetHipError) as e:
+        L.cn_conv2d_dgrad_sa(None, None, None, None, 3, 1, 1, 1, 8, 8, 1, 1, 1, 1, 0, 0, 1, 0, None)
+    assert str(e.value).startswith('cn_conv2d_dgrad_sa failed (rc=-'), str(e.value)
+
+
+def test_value_return_still_returns_its_value():
+    import convnet_amd as ca
+    assert ca._lib.load().cn_conv2d_bnstats_rows(129) == 2

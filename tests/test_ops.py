@@ -236,7 +236,7 @@ def test_dgrad_with_subsampled_addend_equals_dense_addend(mode, dtype):
 @pytest.mark.parametrize('mode', MODES)
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_dgrad_epilogue_bn_backward_reduction(mode, dtype):
-    """cn_conv2d_dgrad_bnbwd + cn_bn_bwd_partials == cn_conv2d_dgrad followed by cn_bn_bwd: the masked
+    """cn_conv2d_dgrad_bnbwd_sa + cn_bn_bwd_partials == cn_conv2d_dgrad_sa followed by cn_bn_bwd: the masked
     gradient g, the per-tile partial sums, and the BatchNorm input/parameter gradients."""
     dev = _dev(mode)
     _f16_emul_subset(mode, dtype)
@@ -273,7 +273,7 @@ def test_dgrad_epilogue_bn_backward_reduction(mode, dtype):
         g_ref = torch.where(on.view(N, H, W, C), dx_plain, torch.zeros_like(dx_plain))
         assert torch.equal(g.cpu(), g_ref.cpu()), (N, H, W, C, K, R, st)
         if 'jdgrad_kernel' in L.cn_last_kernel_name().decode():    # the large 1x1 junctions run on the streaming kernel
-            assert rows == L.cn_conv2d_dgrad_junction_rows(N, H, W, C)
+            assert rows == L.cn_conv2d_dgrad_junction_rows_k(N, H, W, C, K)
         else:
             assert rows == L.cn_conv2d_dgrad_bnbwd_rows(N, H, W, C, st, st)
         assert tuple(partial.shape) == (rows, 2 * C)
