@@ -6,7 +6,10 @@ init_model :16-31, weight-decay filter :34-40), re-expressed as a declarative st
 of hand-written block classes.  ``quantize=True`` (BASELINE config 5; the reference rebinds torch.nn's
 Conv2d / Linear / BatchNorm2d to its simulated-8-bit classes, :387-391) builds the same tree from
 ``convnet.pytorch_amd.quant``'s QConv2d / QLinear / RangeBN.  Out of scope here (not reachable from the
-BASELINE configs): ResNet_cifar, resnet_se, mixed-size "sampled" regimes, checkpoint_segments, bn_norm.
+``bn_norm='L1'`` (the reference rebinds torch.nn's BatchNorm2d to models/modules/lp_norm.py's L1BatchNorm2d, :393-399)
+builds the same tree with ``nn.L1BatchNorm2d`` (csrc/l1bn.hip) for the stem, branch and shortcut norms; such a norm takes
+part in no convolution-epilogue fusion.  Out of scope here (not reachable from the BASELINE configs): ResNet_cifar,
+resnet_se, mixed-size "sampled" regimes, checkpoint_segments, bn_norm='TopK'.
 
 Module construction order and registration order deliberately match the reference, so seeding
 torch's RNG and building ``resnet(depth=50)`` yields bit-identical initial weights.
@@ -39,10 +42,11 @@ _BRANCH = {
 
 def weight_decay_config(value=1e-4, log=False):
     """Regulariser spec of the reference regime (models/resnet.py:34-40): decay every parameter
-    whose name does not end in 'bias' and whose module is not a BatchNorm2d."""
+    whose name does not end in 'bias' and whose module is not a BatchNorm2d (with bn_norm='L1' the reference's
+    nn.BatchNorm2d IS its L1BatchNorm2d by then, so that class is exempt in the same way)."""
     return {'name': 'WeightDecay', 'value': value, 'log': log,
             'filter': {'parameter_name': lambda n: not n.endswith('bias'),
-                       'module': lambda m: not isinstance(m, cnn.BatchNorm2d)}}
+                       'module': lambda m: not isinstance(m, (cnn.BatchNorm2d, cnn.L1BatchNorm2d))}}
 
 
 def linear_scale(lr0, lrT, T, t0=0):
@@ -54,11 +58,11 @@ class ResidualBlock(tnn.Module):
     """BasicBlock / Bottleneck of the reference (models/resnet.py:81-165) built from a branch plan.
     The last BN of the branch fuses `+ residual` and the final ReLU; inner BNs fuse their ReLU."""
 
-    def __init__(self, kind, inplanes, planes, stride, expansion, downsample, op_classes=None, groups=1):
+    def __init__(self, kind, inplanes, planes, stride, expansion, downsample, op_classes=None, groups=1, norm=None):
         super().__init__()
         self.kind = kind
         self.quantized = op_classes is not None
-        Conv, Norm = op_classes[:2] if self.quantized else (cnn.Conv2d, cnn.BatchNorm2d)
+        Conv, Norm = op_classes[:2] if self.quantized else (cnn.Conv2d, norm or cnn.BatchNorm2d)
         widths = {'planes': planes, 'out': planes * expansion}
         cin = inplanes
         self.n_convs = len(_BRANCH[kind])
@@ -66,17 +70,21 @@ class ResidualBlock(tnn.Module):
         # A grouped convolution takes part in no fusion: the BatchNorm it feeds runs its standalone passes, and no
         # BatchNorm parks a lazy operand (or its backward reduction) on it; everything else keeps its fusions.
         self.grouped = [k == 3 and groups > 1 for k, _, _ in _BRANCH[kind]]
+        # norm (bn_norm='L1'): that norm class runs its standalone passes behind EVERY convolution - the same no-fusion
+        # rule, for all of the block's convolutions and its shortcut
+        self.unfused_norm = norm is not None
+        self.nofuse = [g or self.unfused_norm for g in self.grouped]
         for i, (k, wkey, strided) in enumerate(_BRANCH[kind], start=1):
             cout = widths[wkey]
             gkw = {'groups': groups} if self.grouped[i - 1] else {}
             setattr(self, 'conv%d' % i, Conv(cin, cout, kernel_size=k, stride=stride if strided else 1,
                                              padding=k // 2, bias=False, **gkw))
             setattr(self, 'bn%d' % i, Norm(cout))
-            if not self.quantized and not self.grouped[i - 1]:
+            if not self.quantized and not self.nofuse[i - 1]:
                 getattr(self, 'conv%d' % i).feeds_batchnorm = True   # BN statistics come out of the conv epilogue
                 getattr(self, 'conv%d' % i).__dict__['stats_bn'] = getattr(self, 'bn%d' % i)   # ... centred on its running mean
                 getattr(self, 'bn%d' % i).__dict__['producer_conv'] = getattr(self, 'conv%d' % i)   # (lazy dy: ops.LAZY_DY)
-            if i > 1 and not self.quantized and not self.grouped[i - 1] and not self.grouped[i - 2]:   # this conv reads relu(bn_{i-1}(.)): its dgrad epilogue does that BN's backward reduction
+            if i > 1 and not self.quantized and not self.nofuse[i - 1] and not self.nofuse[i - 2]:   # this conv reads relu(bn_{i-1}(.)): its dgrad epilogue does that BN's backward reduction
                 # (instance dict, not setattr: the BN must not become a registered sub-module of the conv)
                 getattr(self, 'conv%d' % i).__dict__['input_bn'] = getattr(self, 'bn%d' % (i - 1))
             if i == 1 and kind == 'basic':
@@ -104,10 +112,11 @@ class ResidualBlock(tnn.Module):
                 self.conv1.__dict__['share_q_out'] = True
                 downsample[0].__dict__['share_q_from'] = self.conv1
             return
-        if self.grouped[0]:
-            # conv1 is grouped (ResNeXt BasicBlock): the two gradients meeting at the block input are added by the fork
+        if self.nofuse[0]:
+            # conv1 is grouped (ResNeXt BasicBlock) or the norms are unfused: the two gradients meeting at the block input
+            # are added by the fork
             self._holder = None
-            if downsample is not None:
+            if downsample is not None and not self.unfused_norm:
                 downsample[0].feeds_batchnorm = True
                 downsample[0].__dict__['stats_bn'] = downsample[1]
                 downsample[1].__dict__['producer_conv'] = downsample[0]
@@ -133,14 +142,14 @@ class ResidualBlock(tnn.Module):
         convolution on the 64-channel halo kernel applies that BatchNorm on its operand path (ops.LAZY_A)."""
         if not self.quantized:
             for i in range(1, self.n_convs):
-                if self.grouped[i - 1] or self.grouped[i]:
+                if self.nofuse[i - 1] or self.nofuse[i]:
                     continue
                 getattr(self, 'bn%d' % i).__dict__['inner_consumer_conv'] = getattr(self, 'conv%d' % (i + 1))
 
     def set_input_bn(self, bn):
         """The block input is the output of `bn` (the previous block's last BN, ReLU and residual fused):
         whichever of conv1 / downsample conv completes the input gradient reduces it for that BN."""
-        if self.quantized:
+        if self.quantized or self.unfused_norm:
             return
         if self.downsample is not None:
             self.downsample[0].__dict__['input_bn'] = bn
@@ -182,7 +191,7 @@ def init_model(model):
         if isinstance(m, cnn.Conv2d):
             n = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
             m.weight.data.normal_(0, math.sqrt(2. / n))
-        elif isinstance(m, cnn.BatchNorm2d):
+        elif isinstance(m, (cnn.BatchNorm2d, cnn.L1BatchNorm2d)):   # (the reference's rebound nn.BatchNorm2d under bn_norm)
             m.weight.data.fill_(1)
             m.bias.data.zero_()
     for m in model.modules():
@@ -198,7 +207,7 @@ class ResNetImagenet(tnn.Module):
     def __init__(self, num_classes=1000, inplanes=64, block='bottleneck', layers=(3, 4, 23, 3),
                  width=(64, 128, 256, 512), expansion=4, regime='normal', scale_lr=1, ramp_up_lr=True,
                  ramp_up_epochs=5, epochs=90, base_devices=4, base_device_batch=64, quantize=False,
-                 groups=(1, 1, 1, 1)):
+                 groups=(1, 1, 1, 1), bn_norm=None):
         super().__init__()
         groups = [int(g) for g in groups]
         if len(groups) != len(layers) or min(groups) < 1:
@@ -206,17 +215,22 @@ class ResNetImagenet(tnn.Module):
         if quantize and max(groups) > 1:
             raise NotImplementedError('quantize=True with grouped convolutions (groups=%r): the quantised operators are '
                                       'dense-only' % (groups,))
+        if bn_norm not in (None, 'L1'):
+            raise NotImplementedError("bn_norm=%r: 'L1' (nn.L1BatchNorm2d) is the norm option built natively" % (bn_norm,))
+        if quantize and bn_norm is not None:
+            raise NotImplementedError('quantize=True together with bn_norm=%r: the quantised model keeps its RangeBN' % (bn_norm,))
+        self.norm = cnn.L1BatchNorm2d if bn_norm == 'L1' else None   # None: nn.BatchNorm2d with every fusion
         self.inplanes = inplanes
         self.op_classes = None
         if quantize:
             from .. import quant
             self.op_classes = (quant.QConv2d, quant.RangeBN, quant.QLinear)
-        Conv, Norm, Dense = self.op_classes or (cnn.Conv2d, cnn.BatchNorm2d, cnn.Linear)
+        Conv, Norm, Dense = self.op_classes or (cnn.Conv2d, self.norm or cnn.BatchNorm2d, cnn.Linear)
         self.conv1 = Conv(3, inplanes, kernel_size=7, stride=2, padding=3, bias=False)
         self.conv1.needs_dgrad = False  # network input needs no gradient
-        self.conv1.feeds_batchnorm = not quantize
+        self.conv1.feeds_batchnorm = not quantize and self.norm is None
         self.bn1 = Norm(inplanes)
-        if not quantize:
+        if not quantize and self.norm is None:
             self.conv1.__dict__['stats_bn'] = self.bn1   # the stem's statistics partials are centred on bn1.running_mean
         self.relu = cnn.ReLU(inplace=True)
         self.maxpool = cnn.MaxPool2d(kernel_size=3, stride=2, padding=1)
@@ -274,14 +288,14 @@ class ResNetImagenet(tnn.Module):
         out_planes = planes * expansion
         downsample = None
         if stride != 1 or self.inplanes != out_planes:  # models/resnet.py:176-181
-            Conv, Norm = (self.op_classes or (cnn.Conv2d, cnn.BatchNorm2d))[:2]
+            Conv, Norm = (self.op_classes or (cnn.Conv2d, self.norm or cnn.BatchNorm2d))[:2]
             downsample = tnn.Sequential(
                 Conv(self.inplanes, out_planes, kernel_size=1, stride=stride, bias=False),
                 Norm(out_planes))
-        stage = [ResidualBlock(kind, self.inplanes, planes, stride, expansion, downsample, self.op_classes, groups)]
+        stage = [ResidualBlock(kind, self.inplanes, planes, stride, expansion, downsample, self.op_classes, groups, self.norm)]
         self.inplanes = out_planes
         for _ in range(1, blocks):
-            stage.append(ResidualBlock(kind, self.inplanes, planes, 1, expansion, None, self.op_classes, groups))
+            stage.append(ResidualBlock(kind, self.inplanes, planes, 1, expansion, None, self.op_classes, groups, self.norm))
         return tnn.Sequential(*stage)
 
     def features(self, x):
@@ -312,10 +326,16 @@ class ResNetImagenet(tnn.Module):
 
 def resnet(**config):
     """Factory with the reference's call shape: resnet(dataset=..., depth=..., **kw); groups=[g1, g2, g3, g4] makes
-    every 3x3 convolution of stage i grouped (the reference's ResNet_imagenet(groups=...), ResNeXt's building block)."""
+    every 3x3 convolution of stage i grouped (the reference's ResNet_imagenet(groups=...), ResNeXt's building block);
+    bn_norm='L1' puts nn.L1BatchNorm2d in the place of every BatchNorm2d (the reference's models/resnet.py:393-399)."""
     dataset = config.pop('dataset', 'imagenet')
-    if config.pop('bn_norm', None):
-        raise NotImplementedError("resnet(bn_norm=...) is not part of the MI355X hot path")
+    bn_norm = config.pop('bn_norm', None) or None
+    if bn_norm == 'TopK':
+        raise NotImplementedError("resnet(bn_norm='TopK') needs a per-channel top-k selection kernel that is not built; "
+                                  "bn_norm='L1' is")
+    if bn_norm is not None and bn_norm != 'L1':
+        raise ValueError("bn_norm must be None or 'L1', got %r" % (bn_norm,))
+    config['bn_norm'] = bn_norm
     config['quantize'] = bool(config.pop('quantize', False))
     if 'imagenet' not in dataset:
         raise NotImplementedError("only the ImageNet ResNet variant is built natively (dataset=%r)" % dataset)

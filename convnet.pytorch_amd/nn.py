@@ -253,6 +253,40 @@ class BatchNorm2d(_ArenaModule):
         return '{}, eps={}, momentum={}'.format(self.num_features, self.eps, self.momentum)
 
 
+class L1BatchNorm2d(_ArenaModule):
+    """L1BatchNorm2d(num_features, momentum, eps) of the reference (models/modules/lp_norm.py:238-291, what
+    resnet(bn_norm='L1') puts in the place of nn.BatchNorm2d), with the fused residual add + ReLU of this package's
+    blocks: ``bn(y, residual=None, relu=False)``.  Normalises by the mean absolute deviation, scale = 1 / (mean|y - mean| *
+    sqrt(pi/2) + eps); `running_var` holds that scale (both buffers start at 0, and the running update keeps `momentum`
+    of the OLD value); no num_batches_tracked; parameters register as bias, weight (the reference's state-dict order).
+    Deliberately not a BatchNorm2d: none of the convolution-epilogue fusions keyed on that class applies."""
+
+    def __init__(self, num_features, dim=1, momentum=0.1, bias=True, normalized=True, eps=1e-5, noise=False):
+        super().__init__()
+        if not normalized or noise or dim != 1 or not bias:
+            raise NotImplementedError('HIP L1BatchNorm2d is the reference default: dim=1, bias=True, normalized=True, '
+                                      'noise=False')
+        self.num_features, self.eps, self.momentum = num_features, eps, momentum
+        self.dim, self.noise = dim, noise
+        self.register_buffer('running_mean', torch.zeros(num_features))
+        self.register_buffer('running_var', torch.zeros(num_features))
+        # (the reference leaves both uninitialised until init_model fills them; (0, 1) here)
+        self.bias = tnn.Parameter(torch.zeros(num_features))
+        self.weight = tnn.Parameter(torch.ones(num_features))
+
+    def forward(self, y, residual=None, relu=False):
+        self._require_prepared()
+        if self.training:
+            if torch.is_grad_enabled():
+                return ops.L1BatchNormActFunction.apply(y, self.weight, self.bias, residual, self, relu)
+            with torch.no_grad():
+                return ops.L1BatchNormActFunction.apply(y, self.weight, self.bias, residual, self, relu)
+        return ops.l1_batch_norm_infer(y, residual, self, relu)
+
+    def extra_repr(self):
+        return '{}, eps={}, momentum={}'.format(self.num_features, self.eps, self.momentum)
+
+
 class ReLU(tnn.Module):
     def __init__(self, inplace=False):
         super().__init__()

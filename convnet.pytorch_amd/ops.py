@@ -1373,6 +1373,88 @@ def batch_norm_infer(y, residual, mod, relu):
     return z
 
 
+class L1BatchNormActFunction(Function):
+    """z = act(L1BN(y) + residual), training mode (nn.L1BatchNorm2d on csrc/l1bn.hip).  Always the standalone passes: the
+    forward reads y three times (mean, mean absolute deviation, apply), the backward is reduce + finalize + apply."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, residual, mod, relu):
+        take_pending_stats(y)     # (sum / sum-of-squares partials of a producer are of no use to this norm)
+        y = y.contiguous()
+        N, H, W, C = y.shape
+        M = N * H * W
+        L = _L()
+        code = dtype_code(y.dtype)
+        if residual is not None:
+            if tuple(residual.shape) != tuple(y.shape) or residual.dtype != y.dtype:
+                raise _lib.ConvNetHipError('L1BatchNorm2d: residual %s %s does not match the input %s %s'
+                                           % (tuple(residual.shape), residual.dtype, tuple(y.shape), y.dtype))
+            residual = residual.contiguous()
+        ws = workspace(L.cn_l1bn_workspace(M, C, code), y.device)
+        z = torch.empty_like(y)
+        stats = torch.empty(7 * C, dtype=torch.float32, device=y.device)
+        mask = None
+        if relu and residual is not None:   # 1 bit per output instead of re-reading z in backward
+            mask = torch.empty(M * (C // _lib.chunk_elems(y.dtype)), dtype=torch.uint8, device=y.device)
+        nb = y.numel() * _esize(y)
+        COUNTERS['l1bn_fwd'] = COUNTERS.get('l1bn_fwd', 0) + 1
+        PROFILER.run('l1bn_sum+l1bn_mean+l1bn_absdev+l1bn_finalize+l1bn_apply', 5, 0.0,
+                     nb * (5 if residual is not None else 4) + (mask.numel() if mask is not None else 0),
+                     lambda: L.cn_l1bn_fwd_train(ptr(y), ptr(residual), ptr(z), ptr(mask), ptr(gamma), ptr(beta),
+                                                 ptr(mod.running_mean), ptr(mod.running_var), float(mod.momentum),
+                                                 mod.eps, ptr(stats), M, C, int(relu), code, ptr(ws), ws.numel() * 4,
+                                                 stream_of(y)),
+                     y.device)
+        ctx.mod = mod
+        ctx.relu = relu
+        ctx.has_res = residual is not None
+        if mask is not None:
+            ctx.save_for_backward(y, stats, mask)
+        else:
+            ctx.save_for_backward(y, stats)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        saved = ctx.saved_tensors
+        y, stats = saved[0], saved[1]
+        zmask = saved[2] if len(saved) > 2 else None
+        mod = ctx.mod
+        N, H, W, C = y.shape
+        M = N * H * W
+        L = _L()
+        code = dtype_code(y.dtype)
+        dz = dz.contiguous()
+        ws = workspace(L.cn_l1bn_workspace(M, C, code), y.device)
+        dy = torch.empty_like(y)
+        dres = torch.empty_like(y) if (ctx.has_res and ctx.needs_input_grad[3]) else None
+        coef = torch.empty(3 * C, dtype=torch.float32, device=y.device)
+        nb = y.numel() * _esize(y)
+        COUNTERS['l1bn_bwd'] = COUNTERS.get('l1bn_bwd', 0) + 1
+        with SIDE.mark(dy):
+            PROFILER.run('l1bn_bwd_reduce+l1bn_bwd_finalize+l1bn_bwd_apply', 3, 0.0,
+                         nb * (5 + (1 if dres is not None else 0)) + (2 * zmask.numel() if zmask is not None else 0),
+                         lambda: L.cn_l1bn_bwd(ptr(dz), ptr(y), ptr(zmask), ptr(mod.weight), ptr(stats), ptr(dy),
+                                               ptr(dres), ptr(mod.grad_view('weight')), ptr(mod.grad_view('bias')),
+                                               1.0, 1.0, ptr(coef), M, C, int(ctx.relu), code, ptr(ws),
+                                               ws.numel() * 4, stream_of(y)),
+                         y.device)
+        mod._notify_grad_ready()
+        return dy, None, None, dres, None, None
+
+
+def l1_batch_norm_infer(y, residual, mod, relu):
+    take_pending_stats(y)
+    y = y.contiguous()
+    N, H, W, C = y.shape
+    z = torch.empty_like(y)
+    coeffs = torch.empty(3 * C, dtype=torch.float32, device=y.device)
+    _L().cn_l1bn_fwd_infer(ptr(y), ptr(residual.contiguous() if residual is not None else None), ptr(z), ptr(mod.weight),
+                           ptr(mod.bias), ptr(mod.running_mean), ptr(mod.running_var), ptr(coeffs), N * H * W, C,
+                           int(relu), dtype_code(y.dtype), stream_of(y))
+    return z
+
+
 class MaxPool2dFunction(Function):
     @staticmethod
     def forward(ctx, x, k, stride, pad):

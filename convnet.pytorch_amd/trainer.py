@@ -712,6 +712,10 @@ class Trainer(object):
 
     def calibrate_bn(self, data_loader, num_steps=None):
         from . import nn as cnn
+        if any(isinstance(m, cnn.L1BatchNorm2d) for m in self.model.modules()):
+            # the reference sets momentum = None on every nn.BatchNorm2d - its L1BatchNorm2d under bn_norm='L1' - and that
+            # class multiplies by its momentum (lp_norm.py:268-272): TypeError there
+            raise NotImplementedError('calibrate_bn is not defined for L1BatchNorm2d (the reference raises TypeError here)')
         for m in self.model.modules():
             if isinstance(m, cnn.BatchNorm2d):
                 m.momentum = None

@@ -310,6 +310,27 @@ cn_status cn_bn_bwd_partials(const void* g, const void* y, const float* gamma, c
                              int M, int C, int dtype, const float* partial, int nrb, void* workspace, size_t ws_bytes,
                              void* stream);
 
+/* ---- L1BatchNorm2d (+ fused residual add + ReLU): resnet(bn_norm='L1') (models/resnet.py:393-399,
+ * models/modules/lp_norm.py:238-291 with normalized=True, noise=False) ---------------------------
+ * Per channel over the M rows: mu = mean y, V = mean|y - mu|, s = 1/(V*sqrt(pi/2) + eps), z = (y - mu)*s*gamma + beta;
+ * running_mean <- running_mean*momentum + mu*(1 - momentum), running_var <- running_var*momentum + s*(1 - momentum)
+ * (the buffer holds the scale; inference is z = (y - running_mean)*running_var*gamma + beta).
+ * stats_out: 7*C floats = [mu | s | gamma*s | beta | mean sign(y - mu) | mu_lo | s_lo] (the lo halves are non-zero only
+ * for M <= 32 values per channel, where the operator runs in float64).  z == NULL: statistics only.  relu_mask as for
+ * cn_bn_fwd_train.  Backward: dy = gamma*s*[(g - mean g) - sqrt(pi/2)*(dgamma/M)*(sign(y - mu) - mean sign)], sign(0) = 0. */
+size_t cn_l1bn_workspace(int M, int C, int dtype);
+cn_status cn_l1bn_fwd_train(const void* y, const void* residual, void* z, unsigned char* relu_mask, const float* gamma,
+                            const float* beta, float* running_mean, float* running_var, float momentum, float eps,
+                            float* stats_out /*7C*/, int M, int C, int relu, int dtype, void* workspace, size_t ws_bytes,
+                            void* stream);
+cn_status cn_l1bn_fwd_infer(const void* y, const void* residual, void* z, const float* gamma, const float* beta,
+                            const float* running_mean, const float* running_var, float* coeffs /*3C*/, int M, int C,
+                            int relu, int dtype, void* stream);
+cn_status cn_l1bn_bwd(const void* dz, const void* y, const unsigned char* relu_mask, const float* gamma, const float* stats,
+                      void* dy, void* dres, float* dgamma, float* dbeta, float beta_acc, float gscale,
+                      float* coef_scratch /*3C*/, int M, int C, int relu, int dtype, void* workspace, size_t ws_bytes,
+                      void* stream);
+
 /* ---- nn.SyncBatchNorm (main.py:190-191, --sync-bn) ----------------------------------------------
  * Each rank reduces its own statistics to 2*C doubles, the caller all-reduces that buffer in-stream
  * (cn_comm_allreduce, dtype 2, on the rank's communicator handle) and passes the global sums and the global row
