@@ -107,3 +107,55 @@ extern "C" cn_status cn_softmax_ce(const float* logits, const long long* target,
   CN_LAUNCH(loss_reduce_kernel, dim3(1), dim3(256), stream, (const float*)row_scratch, B, step_out, meters);
   return cn_check_launch("softmax_ce");
 }
+
+// ---- average over duplicates (trainer.py:32-41 _average_duplicates, batch_first) ---------------------------------------
+// logits[B*D][K], the D rows of a sample consecutive -> mean[B][K]: the sum over d = 0..D-1 in that order in fp32, then a
+// true division by (float)D (torch's mean: sum / count, not a multiply by the reciprocal).
+__global__ __launch_bounds__(256) void avg_duplicates_fwd_kernel(const float* logits, float* mean, long long BK, int D, int K) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= BK) return;
+  const long long b = i / K;
+  const int k = (int)(i - b * K);
+  const float* p = logits + (size_t)b * D * K + k;
+  float s = p[0];
+  for (int d = 1; d < D; ++d) s += p[(size_t)d * K];
+  mean[i] = s / (float)D;
+}
+
+// dlogits[b*D + d][k] = dmean[b][k] / D for every d
+template <typename TG>
+__global__ __launch_bounds__(256) void avg_duplicates_bwd_kernel(const float* dmean, TG* dlogits, long long BK, int D, int K) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= BK) return;
+  const long long b = i / K;
+  const int k = (int)(i - b * K);
+  const float g = dmean[i] / (float)D;
+  TG* o = dlogits + (size_t)b * D * K + k;
+  for (int d = 0; d < D; ++d) cn_store_elem<TG>(o + (size_t)d * K, g);
+}
+
+static bool avg_duplicates_shape_ok(int B, int D, int K, const char* what) {
+  if (B <= 0 || D <= 0 || K <= 0 || ((long long)B * K + 255) / 256 > 0x7fffffffLL) { cn_set_error(what); return false; }
+  return true;
+}
+
+extern "C" cn_status cn_avg_duplicates_fwd(const float* logits, float* mean, int B, int D, int K, void* stream_) {
+  if (logits == nullptr || mean == nullptr) { cn_set_error("avg_duplicates_fwd: null operand"); return CN_EINVAL; }
+  if (!avg_duplicates_shape_ok(B, D, K, "avg_duplicates_fwd: bad shape")) return CN_ESHAPE;
+  const long long BK = (long long)B * K;
+  CN_LAUNCH(avg_duplicates_fwd_kernel, dim3((unsigned)((BK + 255) / 256)), dim3(256), (hipStream_t)stream_, logits, mean, BK, D, K);
+  return cn_check_launch("avg_duplicates_fwd");
+}
+
+extern "C" cn_status cn_avg_duplicates_bwd(const float* dmean, void* dlogits, int grad_dtype, int B, int D, int K, void* stream_) {
+  if (dmean == nullptr || dlogits == nullptr) { cn_set_error("avg_duplicates_bwd: null operand"); return CN_EINVAL; }
+  if (!avg_duplicates_shape_ok(B, D, K, "avg_duplicates_bwd: bad shape")) return CN_ESHAPE;
+  const long long BK = (long long)B * K;
+  const dim3 grid((unsigned)((BK + 255) / 256));
+  hipStream_t stream = (hipStream_t)stream_;
+  if (grad_dtype == CN_BF16) CN_LAUNCH(avg_duplicates_bwd_kernel<bf16_t>, grid, dim3(256), stream, dmean, (bf16_t*)dlogits, BK, D, K);
+  else if (grad_dtype == CN_F16) CN_LAUNCH(avg_duplicates_bwd_kernel<f16_t>, grid, dim3(256), stream, dmean, (f16_t*)dlogits, BK, D, K);
+  else if (grad_dtype == CN_F32) CN_LAUNCH(avg_duplicates_bwd_kernel<float>, grid, dim3(256), stream, dmean, (float*)dlogits, BK, D, K);
+  else { cn_set_error("avg_duplicates_bwd: unknown gradient dtype"); return CN_EINVAL; }
+  return cn_check_launch("avg_duplicates_bwd");
+}

@@ -10,6 +10,8 @@ not part of this image; the same steps are re-stated here on PIL + numpy:
     eval  : Resize(scale_size = input_size*8/7) -> CenterCrop(input_size)
             -> ToTensor -> Normalize                                  preprocess.py:21-41 (scale_crop)
     DataRegime: epoch-keyed loader settings, DistributedSampler       data.py:74-125
+    duplicates = D > 1 ("batch augmentation"): the single-image transform applied D times
+            to the same decoded image, results stacked at dim 0      preprocess.py:105-111 (multi_transform)
 
 Batches leave this module exactly as the reference's loader hands them to `Trainer`: fp32 NCHW
 `inputs`, int64 `target`, pinned when asked.  The device side (copy-stream prefetch, fused cast to the
@@ -236,6 +238,115 @@ def collate_crops(batch):
     return inputs, target
 
 
+class ViewsForDevice(object):
+    """`duplicates` > 1 with the Resize step on the device: ONE uint8 source region (HWC; the bounding box of the views'
+    boxes, cropped from the decoded image once) and one record per view: (horizontal table, vertical table, flip, left, top,
+    w, h), the box relative to the region.  The tables are those of the view's own box, so a view is exactly
+    crop(box).resize(size): no tap reads outside its box."""
+    __slots__ = ('pix', 'views', 'size')
+
+    def __init__(self, pix, views, size):
+        self.pix, self.views, self.size = pix, views, size
+
+
+class RandomResizedCropViews(RandomResizedCrop):
+    """RandomResizedCrop -> RandomHorizontalFlip applied `duplicates` times to one image (multi_transform's order of draws:
+    crop parameters, flip; crop parameters, flip; ...), with the resize and the flip left to the device."""
+
+    def __init__(self, size, duplicates, p=0.5, **kw):
+        super().__init__(size, **kw)
+        self.duplicates, self.p = int(duplicates), p
+
+    def __call__(self, img):
+        draws = []
+        for _ in range(self.duplicates):
+            box = self.get_params(*img.size)
+            draws.append((box, bool(torch.rand(1) < self.p)))      # RandomHorizontalFlip.forward's draw
+        x0, y0 = min(b[0] for b, _ in draws), min(b[1] for b, _ in draws)
+        x1, y1 = max(b[0] + b[2] for b, _ in draws), max(b[1] + b[3] for b, _ in draws)
+        pix = np.array(img.crop((x0, y0, x1, y1)), dtype=np.uint8)
+        views = [(resample_table_cached(cw, self.size), resample_table_cached(ch, self.size), flip, left - x0, top - y0, cw, ch)
+                 for (left, top, cw, ch), flip in draws]
+        return ViewsForDevice(pix, views, self.size)
+
+    def __repr__(self):
+        return 'RandomResizedCropViews(%d, duplicates=%d)' % (self.size, self.duplicates)
+
+
+class ResizeCenterCropViews(object):
+    """scale_crop with `duplicates` > 1 and the resize on the device: the transform is deterministic, so the D views are
+    the same window of the same region (one region, one pair of tables, D records)."""
+
+    def __init__(self, scale_size, size, duplicates):
+        self.one, self.duplicates = ResizeCenterCropForDevice(scale_size, size), int(duplicates)
+
+    def __call__(self, img):
+        c = self.one(img)
+        h, w = c.pix.shape[0], c.pix.shape[1]
+        return ViewsForDevice(c.pix, [(c.th, c.tv, False, 0, 0, w, h)] * self.duplicates, c.size)
+
+    def __repr__(self):
+        return 'ResizeCenterCropViews(%d, %d, duplicates=%d)' % (self.one.scale_size, self.one.size, self.duplicates)
+
+
+VIEW_META = 10      # == RS_VMETA of csrc/resize.hip
+
+
+def collate_views(batch):
+    """collate_fn of a device_resize loader with duplicates > 1: B ViewsForDevice samples of D views -> the flat buffers
+    cn_resize_u8_views takes.  Views are sample-major (b * D + d); a table that several views share (the cached table of
+    one box size, the D identical views of the eval transform) is stored once."""
+    samples = [b[0] for b in batch]
+    target = torch.tensor([b[1] for b in batch], dtype=torch.int64)
+    D = len(samples[0].views)
+    if any(len(s.views) != D for s in samples):
+        raise ValueError('collate_views: samples with different numbers of views')
+    C = samples[0].pix.shape[2]
+    meta = np.zeros((len(samples) * D, VIEW_META), dtype=np.int64)
+    pixels = torch.empty(sum(s.pix.size for s in samples), dtype=torch.uint8)
+    pn = pixels.numpy()
+    tabs, tab_off, tlen = [], {}, 0
+
+    def table(t):
+        nonlocal tlen
+        off = tab_off.get(id(t))
+        if off is None:
+            off = tab_off[id(t)] = tlen
+            tabs.append(t)
+            tlen += t.size
+        return off
+
+    poff = row = v = 0
+    for s in samples:
+        rw = s.pix.shape[1]
+        pn[poff:poff + s.pix.size] = s.pix.reshape(-1)
+        for th, tv, flip, left, top, w, h in s.views:
+            meta[v] = (poff + (top * rw + left) * C, h, w, int(flip), table(th), th.shape[1] - 2, table(tv), tv.shape[1] - 2,
+                       rw * C, row)
+            row += h
+            v += 1
+        poff += s.pix.size
+    tables = torch.from_numpy(np.concatenate([t.reshape(-1) for t in tabs]).astype(np.int32, copy=False))
+    row_owner = np.repeat(np.arange(meta.shape[0], dtype=np.int32), meta[:, 1])
+    inputs = {'views': pixels, 'meta': torch.from_numpy(meta), 'tables': tables, 'row_owner': torch.from_numpy(row_owner),
+              'size': torch.tensor([samples[0].size, C, D], dtype=torch.int32)}
+    return inputs, target
+
+
+class MultiTransform(object):
+    """preprocess.multi_transform: `transform` applied `duplicates` times in sequence to the same image, the results
+    stacked at dim 0 ([D, C, S, S] fp32, or uint8 [D, S, S, C] under device_normalize)."""
+
+    def __init__(self, transform, duplicates):
+        self.transform, self.duplicates = transform, int(duplicates)
+
+    def __call__(self, img):
+        return torch.stack([self.transform(img) for _ in range(self.duplicates)], dim=0)
+
+    def __repr__(self):
+        return 'MultiTransform(%r, duplicates=%d)' % (self.transform, self.duplicates)
+
+
 class ResizeCenterCropForDevice(object):
     """Resize(scale_size) -> CenterCrop(size) (scale_crop) with the resize left to the device: the worker ships the source
     region the size x size centre window of the resized image depends on, and that window's coefficient tables."""
@@ -348,12 +459,15 @@ def inception_preprocess(input_size, normalize=None, device_normalize=False, dev
 def get_transform(transform_name='imagenet', input_size=None, scale_size=None, normalize=None, augment=True,
                   cutout=None, autoaugment=False, padding=None, duplicates=1, num_crops=1, device_normalize=False,
                   device_resize=False):
-    """preprocess.get_transform (preprocess.py:115-161) for the ImageNet family; the research
-    augmentations (autoaugment, cutout, duplicates, multi-crop) are outside the hot path."""
+    """preprocess.get_transform (preprocess.py:115-161) for the ImageNet family, `duplicates` (multi_transform) included;
+    the other research augmentations (autoaugment, cutout, multi-crop) are outside the hot path."""
     if 'imagenet' not in transform_name:
         raise NotImplementedError('transform %r: only the ImageNet pipeline is built' % transform_name)
-    if autoaugment or cutout is not None or duplicates != 1 or num_crops != 1:
-        raise NotImplementedError('autoaugment / cutout / duplicates / multi-crop are not part of the hot path')
+    if autoaugment or cutout is not None or num_crops != 1:
+        raise NotImplementedError('autoaugment / cutout / multi-crop are not part of the hot path')
+    duplicates = int(duplicates)
+    if duplicates < 1:
+        raise ValueError('duplicates must be >= 1, got %d' % duplicates)
     input_size = input_size or 224
     scale_size = scale_size or int(input_size * 8 / 7)
     # device_normalize (not in the reference; main.py turns it on unless --host-normalize is given): the workers stop at the uint8 crop and ToTensor + Normalize
@@ -363,11 +477,20 @@ def get_transform(transform_name='imagenet', input_size=None, scale_size=None, n
     # batch bit for bit, 0.64 of 2.8 ms per image less work in the workers
     if device_resize and not device_normalize:
         raise ValueError('device_resize needs device_normalize (the crops leave the workers as uint8)')
+    # duplicates = D > 1: host / device_normalize stack D results of the single-image transform (multi_transform); under
+    # device_resize the worker draws the D (box, flip) pairs in the same order, ships the bounding region of the boxes ONCE
+    # and the device cuts all D views out of it (cn_resize_u8_views) - the decode is paid once per D training images
+    if duplicates > 1 and device_resize:
+        if augment:
+            return Compose([RandomResizedCropViews(input_size, duplicates)])
+        return Compose([ResizeCenterCropViews(scale_size, input_size, duplicates)])
     if augment:
-        return inception_preprocess(input_size, normalize=normalize, device_normalize=device_normalize,
-                                    device_resize=device_resize)
-    return scale_crop(input_size=input_size, scale_size=scale_size, normalize=normalize, device_normalize=device_normalize,
-                      device_resize=device_resize)
+        one = inception_preprocess(input_size, normalize=normalize, device_normalize=device_normalize,
+                                   device_resize=device_resize)
+    else:
+        one = scale_crop(input_size=input_size, scale_size=scale_size, normalize=normalize, device_normalize=device_normalize,
+                         device_resize=device_resize)
+    return one if duplicates == 1 else MultiTransform(one, duplicates)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -476,7 +599,8 @@ class DataRegime(object):
                 loader['shuffle'] = None
             self._sampler = loader.get('sampler', None)
             if setting['transform'].get('device_resize'):
-                loader.setdefault('collate_fn', collate_crops)
+                loader.setdefault('collate_fn', collate_views if int(setting['transform'].get('duplicates', 1) or 1) > 1
+                                  else collate_crops)
             if loader.get('num_workers', 0) > 0:
                 loader.setdefault('worker_init_fn', _seed_worker)
                 loader.setdefault('persistent_workers', True)

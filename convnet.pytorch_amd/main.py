@@ -74,7 +74,7 @@ def build_parser():
     p.add_argument('--sync-bn', action='store_true', default=False)
     p.add_argument('--mixup', default=None, type=float)
     p.add_argument('--cutmix', default=None, type=float)
-    p.add_argument('--duplicates', default=1, type=int)
+    p.add_argument('--duplicates', default=1, type=int, help='number of augmentations over a single example')
     p.add_argument('--chunk-batch', default=1, type=int)
     p.add_argument('--cutout', action='store_true', default=False)
     p.add_argument('--autoaugment', action='store_true', default=False)
@@ -87,6 +87,10 @@ def build_parser():
     p.add_argument('--adapt-grad-norm', default=None, type=int)
     p.add_argument('--resume', default='', type=str, metavar='PATH')
     p.add_argument('-e', '--evaluate', type=str, metavar='FILE')
+    p.add_argument('--augment', action='store_true', default=False,
+                   help='--evaluate: perform augmentations (evaluate.py: the validation loader uses the training transform)')
+    p.add_argument('--avg-out', action='store_true', default=False,
+                   help='--evaluate: average the outputs of a sample\'s --duplicates views (evaluate.py)')
     p.add_argument('--seed', default=123, type=int)
     p.add_argument('--tensorwatch', action='store_true', default=False)
     p.add_argument('--tensorwatch-port', default=0, type=int)
@@ -98,11 +102,13 @@ def build_parser():
 
 class SyntheticLoader(object):
     """Iterable with __len__ yielding (inputs NCHW fp32, target int64) - the only interface Trainer
-    needs from a loader (trainer.py:198,235).  A small pool of seeded batches is cycled."""
+    needs from a loader (trainer.py:198,235).  A small pool of seeded batches is cycled.  duplicates = D > 1: the inputs
+    are B x D x C x H x W, as a `duplicates` data regime delivers them."""
 
-    def __init__(self, n_batches, batch, size, classes, channels, seed, device=None, pool=8):
+    def __init__(self, n_batches, batch, size, classes, channels, seed, device=None, pool=8, duplicates=1):
         g = torch.Generator().manual_seed(seed)
-        self.pool = [(torch.randn(batch, channels, size, size, generator=g),
+        lead = (batch,) if duplicates == 1 else (batch, duplicates)
+        self.pool = [(torch.randn(*lead, channels, size, size, generator=g),
                       torch.randint(0, classes, (batch,), generator=g)) for _ in range(min(pool, n_batches))]
         if device is not None:
             self.pool = [(x.to(device), t.to(device)) for x, t in self.pool]
@@ -268,11 +274,12 @@ def main_worker(args):
         size = args.input_size or (28 if is_mnist else 224)
         classes, channels = (10, 1) if is_mnist else (model_config.get('num_classes', 1000), 3)
         rank = max(args.local_rank, 0)
-        val_data = SyntheticLoader(args.val_steps, args.eval_batch_size, size, classes, channels, args.seed + 10000)
+        val_data = SyntheticLoader(args.val_steps, args.eval_batch_size, size, classes, channels, args.seed + 10000,
+                                   duplicates=args.duplicates if args.evaluate else 1)
         val_loader = lambda: val_data                                   # noqa: E731
         if not args.evaluate:
             train_data = SyntheticLoader(args.steps_per_epoch, args.batch_size, size, classes, channels,
-                                         args.seed + 1 + rank)
+                                         args.seed + 1 + rank, duplicates=args.duplicates)
             train_loader = lambda: train_data                           # noqa: E731
     else:
         # real image folders through DataRegime, exactly the settings of main.py:264-293
@@ -281,7 +288,11 @@ def main_worker(args):
             raise NotImplementedError('sampled (mixed-size) data regimes are not part of the hot path')
         val_data = DataRegime(getattr(model, 'data_eval_regime', None),
                               defaults={'datasets_path': args.datasets_dir, 'name': args.dataset, 'split': 'val',
-                                        'augment': False, 'input_size': args.input_size,
+                                        # (evaluate.py:181-182: --augment / --duplicates shape the validation loader of an
+                                        # --evaluate run; a training run validates on single centre crops, main.py:266)
+                                        'augment': bool(args.evaluate and args.augment),
+                                        'duplicates': args.duplicates if args.evaluate else 1,
+                                        'input_size': args.input_size,
                                         'batch_size': args.eval_batch_size, 'shuffle': False,
                                         'num_workers': args.workers, 'pin_memory': True, 'drop_last': False,
                                         'device_normalize': not args.host_normalize,
@@ -301,7 +312,7 @@ def main_worker(args):
             train_loader = train_data.get_loader
             logging.info('data regime: %s', train_data)
     if args.evaluate:
-        res = trainer.validate(val_loader())
+        res = trainer.validate(val_loader(), average_output=args.avg_out)
         logging.info(res)
         return res
 

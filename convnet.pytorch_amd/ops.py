@@ -754,6 +754,33 @@ def resize_crops(batch):
     return out
 
 
+def resize_views(batch):
+    """A device_resize loader's batch with duplicates > 1 (data.collate_views, already on the device) -> uint8
+    [B * D, S, S, C], sample-major: every view is PIL's BILINEAR resize of its own box of the sample's shared source region,
+    bit for bit (cn_resize_u8_views), mirrored where the loader drew a flip.  `meta_host` (the meta table in host memory,
+    which the entry point checks the views' bounds on) travels with the batch; a host batch's own meta serves."""
+    px, meta, tables, row_owner = batch['views'], batch['meta'], batch['tables'], batch['row_owner']
+    meta_host = batch.get('meta_host')
+    if meta_host is None:
+        if meta.is_cuda:
+            raise _lib.ConvNetHipError('resize_views: a device batch needs meta_host (the meta table in host memory)')
+        meta_host = meta
+    S, C = (int(v) for v in batch['size'].tolist()[:2])
+    meta_host = meta_host.contiguous()
+    if meta_host.is_cuda or meta_host.dtype != torch.int64 or tuple(meta_host.shape) != tuple(meta.shape) or meta.dim() != 2 \
+            or meta.shape[1] != 10:
+        raise _lib.ConvNetHipError('resize_views: meta / meta_host must be int64 [V, 10], got %s / %s'
+                                   % (tuple(meta.shape), tuple(meta_host.shape)))
+    V, rows = meta.shape[0], row_owner.shape[0]
+    tmp = torch.empty(rows * S * C, dtype=torch.uint8, device=px.device)
+    out = torch.empty((V, S, S, C), dtype=torch.uint8, device=px.device)
+    PROFILER.run('resize_u8_views', 2, 0.0, px.numel() + 2 * tmp.numel() + out.numel(),
+                 lambda: _L().cn_resize_u8_views(ptr(px), ptr(meta), ptr(tables), ptr(row_owner), ptr(tmp), ptr(out),
+                                                 ptr(meta_host), px.numel(), tables.numel(), V, rows, S, C, stream_of(px)),
+                 px.device)
+    return out
+
+
 def u8_nhwc_to_nchw(x_u8, lut):
     """uint8 [N, H, W, C] crops -> the normalised fp32 [N, C, H, W] batch (device-side ToTensor + Normalize)."""
     if x_u8.dtype != torch.uint8 or x_u8.dim() != 4:
@@ -1734,6 +1761,45 @@ class SoftmaxCrossEntropyFunction(Function):
         _L().cn_softmax_ce(ptr(logits), ptr(target), ptr(dlogits), _lib.F32, ptr(row), None, None, B, K,
                            1.0 / B, ptr(go), ctx.crit.smooth_eps, stream_of(logits))
         return dlogits, None, None
+
+
+class AverageDuplicatesFunction(Function):
+    """trainer.py:32-41 _average_duplicates (batch_first): fp32 [B * D, K], the D rows of a sample consecutive -> their
+    mean [B, K] (cn_avg_duplicates_fwd: ordered fp32 sum, true division); backward hands every row dmean / D."""
+
+    @staticmethod
+    def forward(ctx, logits, D):
+        if logits.dim() != 2 or logits.dtype != torch.float32 or D < 1 or logits.shape[0] % D != 0:
+            raise _lib.ConvNetHipError('average_duplicates expects fp32 [B * D, K] logits, got %s %s for D = %d'
+                                       % (logits.dtype, tuple(logits.shape), D))
+        logits = logits.contiguous()
+        B, K = logits.shape[0] // D, logits.shape[1]
+        mean = torch.empty((B, K), dtype=torch.float32, device=logits.device)
+        PROFILER.run('avg_duplicates_fwd', 1, 0.0, (logits.numel() + mean.numel()) * 4,
+                     lambda: _L().cn_avg_duplicates_fwd(ptr(logits), ptr(mean), B, D, K, stream_of(logits)), logits.device)
+        ctx.D = D
+        return mean
+
+    @staticmethod
+    def backward(ctx, dmean):
+        return average_duplicates_bwd(dmean, ctx.D, torch.float32), None
+
+
+def average_duplicates(logits, D):
+    return AverageDuplicatesFunction.apply(logits, int(D))
+
+
+def average_duplicates_bwd(dmean, D, grad_dtype=torch.float32):
+    """dlogits[b * D + d][k] = dmean[b][k] / D in `grad_dtype` (the fp32 quotient rounded once)."""
+    if dmean.dim() != 2 or D < 1:
+        raise _lib.ConvNetHipError('average_duplicates_bwd expects [B, K] and D >= 1, got %s, D = %d' % (tuple(dmean.shape), D))
+    dmean = dmean.contiguous().to(torch.float32)
+    B, K = dmean.shape
+    dlogits = torch.empty((B * D, K), dtype=grad_dtype, device=dmean.device)
+    PROFILER.run('avg_duplicates_bwd', 1, 0.0, dmean.numel() * 4 + dlogits.numel() * _esize(dlogits),
+                 lambda: _L().cn_avg_duplicates_bwd(ptr(dmean), ptr(dlogits), dtype_code(grad_dtype), B, D, K,
+                                                    stream_of(dmean)), dmean.device)
+    return dlogits
 
 
 def accuracy_counts(logits, target):

@@ -12,8 +12,19 @@ What is different by design (MI355X-first):
   (trainer.py:153,225-229); here loss / prec@1 / prec@5 / grad-norm meters accumulate on the device
   and are read back only when a report line is due (values at report points are identical).
 
-Out of the hot path (raise if requested): mixup / cutmix, duplicates + adapt_grad_norm,
-tensorwatch streams, nn.DataParallel.
+Duplicates ("batch augmentation", trainer.py:17-41,199,214-216): a B x D x C x H x W batch is flattened the way the
+reference's `_flatten_duplicates` does - sample-major (a free view, targets repeated D times in place) for
+chunk_batch == 1, view-major (every accumulation chunk holds one view of every sample) for chunk_batch > 1 - and then
+goes through the step as any 4-D batch: graph / plan capture keys on the flattened shape, nothing in the capture policy
+changes.  `average_output=True` averages the model output over each sample's D consecutive rows before the criterion
+(csrc/loss.hip cn_avg_duplicates_fwd / _bwd through ops.average_duplicates), with the targets left unexpanded; such a
+step runs the eager body and is never captured.  The device meters weight a batch by B where the reference weights it by
+B * D: D is constant, the averages are identical.  `average_output` with chunk_batch > 1 is refused: the reference's
+`_average_duplicates` assumes sample-major rows there while the batch is view-major, i.e. it averages rows of
+DIFFERENT samples.
+
+Out of the hot path (raise if requested): mixup / cutmix, adapt_grad_norm (its extra forward / backward passes per
+N steps), tensorwatch streams, nn.DataParallel.
 """
 import ctypes
 import logging
@@ -29,6 +40,22 @@ from ._lib import check, ptr, stream_of
 from .cross_entropy import CrossEntropyLoss
 from .meters import AverageMeter, accuracy
 from .step_policy import (CAPTURE_GRAPH, CAPTURE_PLAN, EAGER, EAGER_TIMED, REPLAY_TIMED, StepPolicy)
+
+
+def flatten_duplicates(inputs, target, batch_first=True, expand_target=True):
+    """trainer.py:17-29 _flatten_duplicates: B x D x ... -> (B*D) x ..., sample-major (batch_first: a view) or view-major;
+    the targets repeated to match unless the outputs are averaged back to B rows."""
+    duplicates = inputs.size(1)
+    if not batch_first:
+        inputs = inputs.transpose(0, 1)
+    inputs = inputs.flatten(0, 1)
+    if expand_target:
+        if batch_first:
+            target = target.view(-1, 1).expand(-1, duplicates)
+        else:
+            target = target.view(1, -1).expand(duplicates, -1)
+        target = target.flatten(0, 1)
+    return inputs, target
 
 
 class DevicePrefetcher(object):
@@ -47,12 +74,22 @@ class DevicePrefetcher(object):
         self._lut = ops.normalize_lut(norm['mean'], norm['std']).to(device) if norm else None
 
     def _finish(self, inputs):
+        dup = None
         if isinstance(inputs, dict):      # device_resize loader: uint8 crops of any size + PIL's resampling tables
-            inputs = ops.resize_crops(inputs)
+            if 'views' in inputs:         # duplicates > 1: D views per shared source region -> [B * D, S, S, C], sample-major
+                dup = int(inputs['size'][2])
+                inputs = ops.resize_views(inputs)
+            else:
+                inputs = ops.resize_crops(inputs)
         if inputs.dtype == torch.uint8:
             if self._lut is None:
                 raise ValueError('uint8 batches need a loader built with device_normalize (mean / std travel with it)')
-            return ops.u8_nhwc_to_nchw(inputs, self._lut)
+            if inputs.dim() == 5:         # host-resized duplicates [B, D, S, S, C]
+                dup = inputs.size(1)
+                inputs = inputs.flatten(0, 1)
+            inputs = ops.u8_nhwc_to_nchw(inputs, self._lut)
+            if dup is not None:           # the reference's loader layout: B x D x C x H x W
+                inputs = inputs.view(inputs.size(0) // dup, dup, *inputs.shape[1:])
         return inputs
 
     def __len__(self):
@@ -66,6 +103,8 @@ class DevicePrefetcher(object):
             with torch.cuda.stream(self.stream):
                 dev_in = {k: (v if k == 'size' else (v if v.is_pinned() else v.pin_memory()).to(self.device, non_blocking=True))
                           for k, v in inputs.items()}
+                if 'views' in inputs:
+                    dev_in['meta_host'] = inputs['meta']     # (cn_resize_u8_views checks the views' bounds on the host copy)
                 x = self._finish(dev_in)
                 t = target.to(self.device, non_blocking=True)
                 ev = torch.cuda.Event()
@@ -306,7 +345,17 @@ class Trainer(object):
 
     def _step(self, inputs_batch, target_batch, training=False, average_output=False, chunk_batch=1):
         if average_output:
-            raise NotImplementedError('average_output (duplicates) is outside the MI355X hot path')
+            if chunk_batch > 1:
+                raise NotImplementedError('average_output with chunk_batch > 1: the reference flattens view-major there and '
+                                          'then averages consecutive rows, i.e. rows of different samples')
+            if target_batch.size(0) == 0 or inputs_batch.size(0) % target_batch.size(0) != 0:
+                raise ValueError('average_output: %d input rows do not divide into %d targets'
+                                 % (inputs_batch.size(0), target_batch.size(0)))
+            if training:
+                self.optimizer.update(self.epoch, self.training_steps)
+            # (eager body, never captured: the capture keys and static buffers know nothing of the averaging)
+            return self._body(inputs_batch, target_batch, training, chunk_batch,
+                              duplicates=inputs_batch.size(0) // target_batch.size(0))
         if training:
             # host side of trainer.py:111-112 (the regime moves lr / momentum; nothing here touches the device
             # except a tiny H2D copy when the schedule changes)
@@ -322,7 +371,7 @@ class Trainer(object):
                 return self._watched_eager_step(rec, inputs_batch, target_batch, chunk_batch)
         return self._body(inputs_batch, target_batch, training, chunk_batch)
 
-    def _body(self, inputs_batch, target_batch, training, chunk_batch):
+    def _body(self, inputs_batch, target_batch, training, chunk_batch, duplicates=None):
         """Device side of one step (trainer.py:106-177): everything here is a stream of kernel launches with
         no host synchronisation, which is what lets `_graph_step` capture it into one HIP graph."""
         outputs = []
@@ -343,6 +392,11 @@ class Trainer(object):
                 self.optimizer.pre_forward()
 
             output = self.model(inputs)
+            if duplicates is not None:      # average_output: mean over each sample's consecutive rows (trainer.py:137-142)
+                if isinstance(output, (list, tuple)):
+                    output = [ops.average_duplicates(o, duplicates) if o is not None else None for o in output]
+                else:
+                    output = ops.average_duplicates(output, duplicates)
             loss = self.criterion(output, target)
 
             if chunk_batch > 1:
@@ -656,10 +710,14 @@ class Trainer(object):
         n_batches = len(data_loader)
         try:
             for i, (inputs, target) in enumerate(DevicePrefetcher(data_loader, self.device)):
-                if inputs.dim() > 4:
-                    raise NotImplementedError('duplicates (B x D x C x H x W inputs) are outside the hot path')
                 meters['data'].update(time.time() - end)
                 self._data_wait_ms = meters['data'].val * 1e3     # (EagerWatch: not the step's own time)
+                if inputs.dim() > 4:     # duplicates: B x D x C x H x W (trainer.py:199,214-216)
+                    inputs, target = flatten_duplicates(inputs, target, batch_first=chunk_batch == 1,
+                                                        expand_target=not average_output)
+                elif average_output:
+                    raise ValueError('average_output needs a batch with a duplicates dimension (B x D x C x H x W), got %s'
+                                     % (tuple(inputs.shape),))
 
                 output, loss, grad = self._step(inputs, target, training=training,
                                                 average_output=average_output, chunk_batch=chunk_batch)

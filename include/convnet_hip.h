@@ -393,6 +393,16 @@ cn_status cn_u8_nhwc_to_nchw_lut(const unsigned char* x_nhwc, float* y_nchw, int
 cn_status cn_resize_u8_crops(const unsigned char* pixels, const long long* meta, const int* tables, const int* row_owner,
                              const int* row_off, unsigned char* tmp, unsigned char* out, int B, int total_rows, int S, int C,
                              void* stream);
+/* the same resize for VIEWS THAT SHARE A SOURCE (batch augmentation, preprocess.py:105-111 multi_transform: D augmented views
+ * of one decoded image): the worker ships the bounding region of a sample's D boxes once, every view is a window of it.
+ * V = B * D views, sample-major (v = b * D + d) -> out[V][S][S][C].  meta[V][10] = the eight entries of cn_resize_u8_crops -
+ * the byte offset being that of the view's first pixel - plus {source row stride in bytes (the region's width * C), first row
+ * of the view in tmp}; the tables are those of the view's own box (crop-then-resize: no tap reads outside it).  meta_host is
+ * the same table in HOST memory: the entry checks on it that every view lies inside pixels (pixel_bytes), tmp (total_rows rows
+ * of S * C bytes) and tables (table_len int32 values), and that stride >= w * C, before anything is launched. */
+cn_status cn_resize_u8_views(const unsigned char* pixels, const long long* meta, const int* tables, const int* row_owner,
+                             unsigned char* tmp, unsigned char* out, const long long* meta_host, long long pixel_bytes,
+                             long long table_len, int V, int total_rows, int S, int C, void* stream);
 /* Stride-2 stem (models/resnet.py:226, 7x7/2 pad 3 on 3 channels) in "pixel pair" form: the fp32 NCHW batch
  * becomes a zero-padded bf16 image [N][H+2*pad_h][(W+2*pad_w)/2][8] whose 16-byte chunks hold two adjacent
  * pixels x 4 channels; with the filter packed the same way (cn_weight_prep_pairs: [K][R][ceil(S/2)][8]) the
@@ -416,6 +426,11 @@ cn_status cn_softmax_ce(const float* logits, const long long* target, void* dlog
                         float* row_scratch, float* step_out, float* meters, int B, int K, float gscale,
                         const float* gscale_dev /*optional device scalar folded into gscale*/, float smooth_eps,
                         void* stream);
+/* trainer.py:32-41 _average_duplicates (batch_first): logits fp32 [B*D][K], the D rows of a sample consecutive ->
+ * mean[B][K] = (sum over d = 0..D-1, in that order, fp32) / (float)D - a true division, as torch's mean.  Backward:
+ * dlogits[b*D + d][k] = dmean[b][k] / D in grad_dtype (rounded once from the fp32 quotient). */
+cn_status cn_avg_duplicates_fwd(const float* logits, float* mean, int B, int D, int K, void* stream);
+cn_status cn_avg_duplicates_bwd(const float* dmean, void* dlogits, int grad_dtype, int B, int D, int K, void* stream);
 
 /* ---- optimizer.step / grad clipping / filter preparation (trainer.py:165-173) --------------- */
 /* hyper_dev (optional, DEVICE, 2 floats {lr, momentum}): when given it overrides the lr / momentum arguments, so
