@@ -38,6 +38,135 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, floa
   }
 }
 
+// ---- Adam / AdamW, RMSprop, Nesterov SGD: the same streaming shape as sgd_kernel, arithmetic of torch.optim's
+// single-tensor (non-foreach, non-maximize) path.  The effective gradient is g' = g*gscale*clip + wd*p (loss scale,
+// clip, WeightDecay regulariser: the reference's order), every state buffer is fp32.  Padding (p = g = state = 0) stays
+// exactly 0 as long as eps > 0: 0 / (0 + eps) = 0.
+//
+// The step count lives on the device: optim_advance_kernel (one thread, once per optimizer step, part of a captured
+// step) increments it and writes the two bias corrections the Adam kernel reads, computed in double from the integer t.
+// om1 / om2 are 1 - beta1, 1 - beta2 as the caller rounded them from double: 1 - beta^t = -expm1(t * log1p(-om)) keeps
+// the complement's precision (1.f - 0.999f is off by 1e-5 relative, which is what a powf of the float beta would start from).
+__global__ void optim_advance_kernel(long long* step, float* corr, float om1, float om2) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const long long t = step[0] + 1;
+  step[0] = t;
+  corr[0] = om1 >= 1.f ? 1.f : (float)(-expm1((double)t * log1p(-(double)om1)));
+  corr[1] = om2 >= 1.f ? 1.f : (float)sqrt(-expm1((double)t * log1p(-(double)om2)));
+}
+
+// torch: m.lerp_(g', 1 - b1); v = v*b2 + ((1 - b2)*g')*g'; p -= (lr/bc1 * m) / (sqrt(v)/sqrt(bc2) + eps), after
+// p *= 1 - lr*wdd for AdamW (wdd = 0: the factor is exactly 1).  corr = {1 - b1^t, sqrt(1 - b2^t)}.
+struct adam_consts { float cs, wd, om1, b2, om2, eps, decay, step_size, bc2s; };
+static __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const adam_consts& c) {
+  const float gg = fmaf(c.wd, p, g * c.cs);
+  p *= c.decay;
+  m = c.om1 < 0.5f ? m + c.om1 * (gg - m) : gg - (gg - m) * (1.f - c.om1);
+  v = fmaf(c.om2 * gg, gg, v * c.b2);
+  const float denom = sqrtf(v) / c.bc2s + c.eps;
+  p -= (c.step_size * m) / denom;
+}
+__global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, long long n, float lr,
+                                                  float om1, float b2, float om2, float eps, float wd, float wdd,
+                                                  float gscale, const float* clip_coef, const float* hyper,
+                                                  const float* corr) {
+  if (hyper != nullptr) lr = hyper[0];
+  adam_consts c;
+  c.cs = clip_coef != nullptr ? gscale * clip_coef[0] : gscale;
+  c.wd = wd; c.om1 = om1; c.b2 = b2; c.om2 = om2; c.eps = eps;
+  c.decay = fmaf(-lr, wdd, 1.f);
+  c.step_size = lr / corr[0];
+  c.bc2s = corr[1];
+  const long long n4 = n >> 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    f32x4 pv = ((const f32x4*)p)[i], gv = ((const f32x4*)g)[i], mv = ((const f32x4*)m)[i], vv = ((const f32x4*)v)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = pv[e], me = mv[e], ve = vv[e];
+      adam_elem(pe, gv[e], me, ve, c);
+      pv[e] = pe; mv[e] = me; vv[e] = ve;
+    }
+    ((f32x4*)p)[i] = pv;
+    ((f32x4*)m)[i] = mv;
+    ((f32x4*)v)[i] = vv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long long i = (n4 << 2) + threadIdx.x;
+    adam_elem(p[i], g[i], m[i], v[i], c);
+  }
+}
+
+// torch (centered = False): sq = sq*alpha + ((1 - alpha)*g')*g'; avg = sqrt(sq) + eps;
+// MOM: buf = mu*buf + g'/avg; p -= lr*buf.  Otherwise p -= (lr*g')/avg (buf is not touched and may be null).
+template <bool MOM>
+static __device__ __forceinline__ void rmsprop_elem(float& p, float g, float& sq, float* buf, float cs, float wd,
+                                                    float alpha, float oma, float eps, float lr, float mu) {
+  const float gg = fmaf(wd, p, g * cs);
+  sq = fmaf(oma * gg, gg, sq * alpha);
+  const float avg = sqrtf(sq) + eps;
+  if (MOM) {
+    *buf = fmaf(mu, *buf, gg / avg);
+    p = fmaf(-lr, *buf, p);
+  } else {
+    p -= (lr * gg) / avg;
+  }
+}
+template <bool MOM>
+__global__ __launch_bounds__(256) void rmsprop_kernel(float* p, const float* g, float* sq, float* buf, long long n,
+                                                     float lr, float mu, float alpha, float oma, float eps, float wd,
+                                                     float gscale, const float* clip_coef, const float* hyper) {
+  if (hyper != nullptr) { lr = hyper[0]; mu = hyper[1]; }
+  const float cs = clip_coef != nullptr ? gscale * clip_coef[0] : gscale;
+  const long long n4 = n >> 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    f32x4 pv = ((const f32x4*)p)[i], gv = ((const f32x4*)g)[i], sv = ((const f32x4*)sq)[i], bv = {0.f, 0.f, 0.f, 0.f};
+    if (MOM) bv = ((const f32x4*)buf)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = pv[e], se = sv[e], be = bv[e];
+      rmsprop_elem<MOM>(pe, gv[e], se, &be, cs, wd, alpha, oma, eps, lr, mu);
+      pv[e] = pe; sv[e] = se; bv[e] = be;
+    }
+    ((f32x4*)p)[i] = pv;
+    ((f32x4*)sq)[i] = sv;
+    if (MOM) ((f32x4*)buf)[i] = bv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long long i = (n4 << 2) + threadIdx.x;
+    rmsprop_elem<MOM>(p[i], g[i], sq[i], MOM ? buf + i : nullptr, cs, wd, alpha, oma, eps, lr, mu);
+  }
+}
+
+// torch (nesterov = True, dampening = 0): buf = mu*buf + g'; p -= lr*(g' + mu*buf).
+static __device__ __forceinline__ void nesterov_elem(float& p, float g, float& buf, float cs, float wd, float lr,
+                                                     float mu) {
+  const float gg = fmaf(wd, p, g * cs);
+  buf = fmaf(mu, buf, gg);
+  p = fmaf(-lr, fmaf(mu, buf, gg), p);
+}
+__global__ __launch_bounds__(256) void sgd_nesterov_kernel(float* p, const float* g, float* buf, long long n, float lr,
+                                                          float momentum, float wd, float gscale,
+                                                          const float* clip_coef, const float* hyper) {
+  if (hyper != nullptr) { lr = hyper[0]; momentum = hyper[1]; }
+  const float cs = clip_coef != nullptr ? gscale * clip_coef[0] : gscale;
+  const long long n4 = n >> 2;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    f32x4 pv = ((const f32x4*)p)[i], gv = ((const f32x4*)g)[i], bv = ((const f32x4*)buf)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = pv[e], be = bv[e];
+      nesterov_elem(pe, gv[e], be, cs, wd, lr, momentum);
+      pv[e] = pe; bv[e] = be;
+    }
+    ((f32x4*)p)[i] = pv;
+    ((f32x4*)buf)[i] = bv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long long i = (n4 << 2) + threadIdx.x;
+    nesterov_elem(p[i], g[i], buf[i], cs, wd, lr, momentum);
+  }
+}
+
 // Sum of squares: partial per workgroup, then cn_clip_coef reduces in fixed order.
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* g, long long n, float* partial) {
   __shared__ float red[4];
@@ -273,6 +402,62 @@ extern "C" cn_status cn_sgd_momentum(float* p, const float* g, float* buf, long 
   CN_LAUNCH(sgd_kernel, dim3(opt_grid(n / 4 + 1, 4096)), dim3(256), (hipStream_t)stream, p, g, buf, n, lr,
             momentum, weight_decay, gscale, clip_coef, hyper_dev);
   return cn_check_launch("sgd_momentum");
+}
+
+static bool opt_misaligned(const char* who, const void* a, const void* b, const void* c, const void* d) {
+  if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0) return false;
+  cn_set_error("%s: buffers must be 16-byte aligned", who);
+  return true;
+}
+
+extern "C" cn_status cn_optim_advance(long long* step_dev, float* corr_dev, float one_minus_beta1,
+                                      float one_minus_beta2, void* stream) {
+  if (step_dev == nullptr || corr_dev == nullptr) { cn_set_error("optim_advance: null state"); return CN_EINVAL; }
+  if (!(one_minus_beta1 > 0.f && one_minus_beta1 <= 1.f && one_minus_beta2 > 0.f && one_minus_beta2 <= 1.f)) {
+    cn_set_error("optim_advance: need 0 <= beta < 1");
+    return CN_EINVAL;
+  }
+  CN_LAUNCH(optim_advance_kernel, dim3(1), dim3(64), (hipStream_t)stream, step_dev, corr_dev, one_minus_beta1,
+            one_minus_beta2);
+  return cn_check_launch("optim_advance");
+}
+
+extern "C" cn_status cn_adam(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long long n, float lr,
+                             float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
+                             float decoupled_decay, float gscale, const float* clip_coef, const float* hyper_dev,
+                             const float* corr_dev, void* stream) {
+  if (n <= 0) return CN_OK;
+  if (corr_dev == nullptr) { cn_set_error("adam: corr_dev (cn_optim_advance writes it) is required"); return CN_EINVAL; }
+  if (opt_misaligned("adam", p, g, exp_avg, exp_avg_sq)) return CN_EINVAL;
+  CN_LAUNCH(adam_kernel, dim3(opt_grid(n / 4 + 1, 4096)), dim3(256), (hipStream_t)stream, p, g, exp_avg, exp_avg_sq, n,
+            lr, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay, decoupled_decay, gscale, clip_coef,
+            hyper_dev, corr_dev);
+  return cn_check_launch("adam");
+}
+
+extern "C" cn_status cn_rmsprop(float* p, const float* g, float* square_avg, float* buf, long long n, float lr,
+                                float momentum, float alpha, float one_minus_alpha, float eps, float weight_decay,
+                                float gscale, const float* clip_coef, const float* hyper_dev, void* stream) {
+  if (n <= 0) return CN_OK;
+  if (opt_misaligned("rmsprop", p, g, square_avg, buf)) return CN_EINVAL;
+  const dim3 grid(opt_grid(n / 4 + 1, 4096));
+  if (buf != nullptr)
+    CN_LAUNCH(rmsprop_kernel<true>, grid, dim3(256), (hipStream_t)stream, p, g, square_avg, buf, n, lr, momentum,
+              alpha, one_minus_alpha, eps, weight_decay, gscale, clip_coef, hyper_dev);
+  else
+    CN_LAUNCH(rmsprop_kernel<false>, grid, dim3(256), (hipStream_t)stream, p, g, square_avg, buf, n, lr, momentum,
+              alpha, one_minus_alpha, eps, weight_decay, gscale, clip_coef, hyper_dev);
+  return cn_check_launch("rmsprop");
+}
+
+extern "C" cn_status cn_sgd_nesterov(float* p, const float* g, float* buf, long long n, float lr, float momentum,
+                                     float weight_decay, float gscale, const float* clip_coef, const float* hyper_dev,
+                                     void* stream) {
+  if (n <= 0) return CN_OK;
+  if (opt_misaligned("sgd_nesterov", p, g, buf, nullptr)) return CN_EINVAL;
+  CN_LAUNCH(sgd_nesterov_kernel, dim3(opt_grid(n / 4 + 1, 4096)), dim3(256), (hipStream_t)stream, p, g, buf, n, lr,
+            momentum, weight_decay, gscale, clip_coef, hyper_dev);
+  return cn_check_launch("sgd_nesterov");
 }
 
 #define CN_NORM_PARTS 1024

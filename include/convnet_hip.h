@@ -438,6 +438,32 @@ cn_status cn_avg_duplicates_bwd(const float* dmean, void* dlogits, int grad_dtyp
 cn_status cn_sgd_momentum(float* p, const float* g, float* buf, long long n, float lr, float momentum,
                           float weight_decay, float gscale, const float* clip_coef, const float* hyper_dev,
                           void* stream);
+/* The other torch.optim steps over the same flat fp32 buffers (single-tensor, non-foreach arithmetic).  Common to all:
+ * the effective gradient is g*gscale*clip_coef[0] + weight_decay*p (the coupled L2 term of the WeightDecay regulariser),
+ * state buffers are fp32 and 16-byte aligned like p and g (CN_EINVAL otherwise, nothing is launched), hyper_dev
+ * (optional, DEVICE, {lr, momentum}) overrides lr / momentum as it does for cn_sgd_momentum, and padding (p = g = state
+ * = 0) stays exactly 0 while eps > 0.  A `one_minus_x` argument is 1 - x rounded to float from the caller's double: the
+ * float difference 1.f - 0.999f is 1e-5 off, which the second moment would inherit.
+ *
+ * cn_optim_advance: step_dev[0] += 1 (the step count t lives on the device, one call per optimizer step, captured with
+ * it), corr_dev[0] = 1 - beta1^t, corr_dev[1] = sqrt(1 - beta2^t), in double from the integer t. */
+cn_status cn_optim_advance(long long* step_dev, float* corr_dev, float one_minus_beta1, float one_minus_beta2,
+                           void* stream);
+/* Adam, and AdamW with decoupled_decay != 0 (p *= 1 - lr*decoupled_decay first).  corr_dev: as cn_optim_advance left
+ * it for this step.  p -= (lr/corr[0]) * m / (sqrt(v)/corr[1] + eps). */
+cn_status cn_adam(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long long n, float lr,
+                  float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
+                  float decoupled_decay, float gscale, const float* clip_coef, const float* hyper_dev,
+                  const float* corr_dev, void* stream);
+/* RMSprop, centered = False.  buf != NULL: the momentum form (buf = momentum*buf + g'/avg, p -= lr*buf); buf == NULL:
+ * p -= lr*g'/avg and momentum is ignored. */
+cn_status cn_rmsprop(float* p, const float* g, float* square_avg, float* buf /*optional*/, long long n, float lr,
+                     float momentum, float alpha, float one_minus_alpha, float eps, float weight_decay, float gscale,
+                     const float* clip_coef, const float* hyper_dev, void* stream);
+/* SGD with nesterov = True, dampening = 0: buf = momentum*buf + g', p -= lr*(g' + momentum*buf). */
+cn_status cn_sgd_nesterov(float* p, const float* g, float* buf, long long n, float lr, float momentum,
+                          float weight_decay, float gscale, const float* clip_coef, const float* hyper_dev,
+                          void* stream);
 size_t cn_grad_norm_workspace(void);
 /* out2[0] = ||g||_2 * gscale, out2[1] = min(1, max_norm/(norm+1e-6)) (1 when max_norm <= 0). */
 cn_status cn_grad_norm_clip(const float* g, long long n, float gscale, float max_norm, float* out2, float* meters2,
