@@ -989,7 +989,7 @@ def test_exact(mode, name):
 
 
 # kernel families (regular expressions on cn_last_kernel_name) the exact sweep must reach.  gpu: every family that
-# cn_set_last_kernel can report outside qconv_i8.hip; emul: the ones reachable at emulator cost (all but the shapes that
+# cn_set_last_kernel can report outside qconv_i8.hip (that one has its own exact file, test_qconv_exact.py); emul: the ones reachable at emulator cost (all but the shapes that
 # exist only at the training batch - none today: every family has a small instantiation)
 FAMILIES_EMUL = {
     'igemm 64-channel tile, register-staged': r'igemm_kernel<\w+, 1, 4, 2, 1, 1, false, false, false, false, false, false>',
