@@ -5,11 +5,14 @@ as /root/reference models/resnet.py (factory :385-431, ResNet_imagenet :216-317,
 init_model :16-31, weight-decay filter :34-40), re-expressed as a declarative stage table instead
 of hand-written block classes.  ``quantize=True`` (BASELINE config 5; the reference rebinds torch.nn's
 Conv2d / Linear / BatchNorm2d to its simulated-8-bit classes, :387-391) builds the same tree from
-``convnet.pytorch_amd.quant``'s QConv2d / QLinear / RangeBN.  Out of scope here (not reachable from the
+``convnet.pytorch_amd.quant``'s QConv2d / QLinear / RangeBN.
 ``bn_norm='L1'`` (the reference rebinds torch.nn's BatchNorm2d to models/modules/lp_norm.py's L1BatchNorm2d, :393-399)
 builds the same tree with ``nn.L1BatchNorm2d`` (csrc/l1bn.hip) for the stem, branch and shortcut norms; such a norm takes
-part in no convolution-epilogue fusion.  Out of scope here (not reachable from the BASELINE configs): ResNet_cifar,
-resnet_se, mixed-size "sampled" regimes, checkpoint_segments, bn_norm='TopK'.
+part in no convolution-epilogue fusion.  ``resnet_se`` (:434-436 there: resnet(residual_block=SEBlock)) constructs ONE
+``nn.SEBlock`` (csrc/se.hip) per stage, hands that same module to every block of the stage and applies it to the SHORTCUT
+(z = relu(bn_last(y) + se(r)), r the block input or the shortcut BatchNorm's output); every fusion that rests on the
+junction reading the untouched block input is off in such a model.  Out of scope here (not reachable from the BASELINE
+configs): ResNet_cifar, mixed-size "sampled" regimes, checkpoint_segments, bn_norm='TopK'.
 
 Module construction order and registration order deliberately match the reference, so seeding
 torch's RNG and building ``resnet(depth=50)`` yields bit-identical initial weights.
@@ -21,7 +24,7 @@ import torch.nn as tnn
 
 from .. import nn as cnn
 
-__all__ = ['resnet']
+__all__ = ['resnet', 'resnet_se']
 
 # depth -> (block kind, blocks per stage)      (reference models/resnet.py:403-419)
 _IMAGENET_DEPTHS = {
@@ -58,9 +61,18 @@ class ResidualBlock(tnn.Module):
     """BasicBlock / Bottleneck of the reference (models/resnet.py:81-165) built from a branch plan.
     The last BN of the branch fuses `+ residual` and the final ReLU; inner BNs fuse their ReLU."""
 
-    def __init__(self, kind, inplanes, planes, stride, expansion, downsample, op_classes=None, groups=1, norm=None):
+    def __init__(self, kind, inplanes, planes, stride, expansion, downsample, op_classes=None, groups=1, norm=None,
+                 residual_block=None):
         super().__init__()
         self.kind = kind
+        # residual_block (resnet_se: the stage's shared nn.SEBlock) gates the shortcut before the junction.  The junction
+        # then no longer reads the untouched block input, so everything resting on that is off: no ResGradHolder (the
+        # fork adds the two block-input gradients), no junction_conv1, no input_bn / consumer_conv across the block
+        # boundary (set_input_bn), no dual apply of the shortcut BatchNorm (its output is pooled first).  The fusions
+        # INSIDE the branch and the projection's statistics epilogue do not see the shortcut and stay.
+        self.gated = residual_block is not None
+        if self.gated and (op_classes is not None or norm is not None):
+            raise NotImplementedError('residual_block together with quantize / bn_norm')
         self.quantized = op_classes is not None
         Conv, Norm = op_classes[:2] if self.quantized else (cnn.Conv2d, norm or cnn.BatchNorm2d)
         widths = {'planes': planes, 'out': planes * expansion}
@@ -94,6 +106,7 @@ class ResidualBlock(tnn.Module):
             self.relu = cnn.ReLU(inplace=True)
             self.dropout = cnn.Dropout(0)
         self.downsample = downsample
+        self.residual_block = residual_block    # (registered behind downsample, as in the reference's blocks)
         if kind == 'basic':
             self.dropout = cnn.Dropout(0)
         self.stride = stride
@@ -112,9 +125,9 @@ class ResidualBlock(tnn.Module):
                 self.conv1.__dict__['share_q_out'] = True
                 downsample[0].__dict__['share_q_from'] = self.conv1
             return
-        if self.nofuse[0]:
-            # conv1 is grouped (ResNeXt BasicBlock) or the norms are unfused: the two gradients meeting at the block input
-            # are added by the fork
+        if self.nofuse[0] or self.gated:
+            # conv1 is grouped (ResNeXt BasicBlock), the norms are unfused or the shortcut is gated: the two gradients
+            # meeting at the block input are added by the fork
             self._holder = None
             if downsample is not None and not self.unfused_norm:
                 downsample[0].feeds_batchnorm = True
@@ -149,7 +162,7 @@ class ResidualBlock(tnn.Module):
     def set_input_bn(self, bn):
         """The block input is the output of `bn` (the previous block's last BN, ReLU and residual fused):
         whichever of conv1 / downsample conv completes the input gradient reduces it for that BN."""
-        if self.quantized or self.unfused_norm:
+        if self.quantized or self.unfused_norm or self.gated:
             return
         if self.downsample is not None:
             self.downsample[0].__dict__['input_bn'] = bn
@@ -175,12 +188,14 @@ class ResidualBlock(tnn.Module):
         if self.downsample is not None:
             ds_conv, ds_bn = self.downsample[0], self.downsample[1]
             from .. import ops
-            if ops.DUAL_BN and ds_bn.training and self.last_bn().training and isinstance(ds_bn, cnn.BatchNorm2d) \
+            if ops.DUAL_BN and not self.gated and ds_bn.training and self.last_bn().training and isinstance(ds_bn, cnn.BatchNorm2d) \
                     and ops._sync_group(ds_bn) is None and ops._sync_group(self.last_bn()) is None:
                 # the shortcut BatchNorm finalises its statistics only; the junction's apply pass applies both
                 residual = ds_bn(ds_conv(xb), defer_apply=True)
                 return self.last_bn()(out, residual=residual, relu=True, residual_bn=ds_bn)
             residual = ds_bn(ds_conv(xb))
+        if self.gated:
+            residual = self.residual_block(residual)
         return self.last_bn()(out, residual=residual, relu=True)
 
 
@@ -207,8 +222,11 @@ class ResNetImagenet(tnn.Module):
     def __init__(self, num_classes=1000, inplanes=64, block='bottleneck', layers=(3, 4, 23, 3),
                  width=(64, 128, 256, 512), expansion=4, regime='normal', scale_lr=1, ramp_up_lr=True,
                  ramp_up_epochs=5, epochs=90, base_devices=4, base_device_batch=64, quantize=False,
-                 groups=(1, 1, 1, 1), bn_norm=None):
+                 groups=(1, 1, 1, 1), bn_norm=None, residual_block=None):
         super().__init__()
+        if residual_block is not None and (quantize or bn_norm is not None):
+            raise NotImplementedError('residual_block (resnet_se) together with quantize=True or bn_norm=%r: the gated '
+                                      'shortcut is built for the default operators only' % (bn_norm,))
         groups = [int(g) for g in groups]
         if len(groups) != len(layers) or min(groups) < 1:
             raise ValueError('groups must give one positive group count per stage, got %r' % (groups,))
@@ -236,7 +254,8 @@ class ResNetImagenet(tnn.Module):
         self.maxpool = cnn.MaxPool2d(kernel_size=3, stride=2, padding=1)
         for i, nblocks in enumerate(layers):
             setattr(self, 'layer%d' % (i + 1),
-                    self._make_layer(block, width[i], nblocks, expansion, stride=1 if i == 0 else 2, groups=groups[i]))
+                    self._make_layer(block, width[i], nblocks, expansion, stride=1 if i == 0 else 2, groups=groups[i],
+                                     residual_block=residual_block))
         prev = None
         for m in self.modules():   # registration order = execution order of the residual blocks
             if isinstance(m, ResidualBlock):
@@ -284,7 +303,7 @@ class ResNetImagenet(tnn.Module):
             self.regime[0]['step_lambda'] = linear_scale(0.1, 0.1 * scale_lr, ramp_up_steps)
             self.regime.insert(1, {'epoch': ramp_up_epochs, 'lr': scale_lr * 1e-1})
 
-    def _make_layer(self, kind, planes, blocks, expansion, stride, groups=1):
+    def _make_layer(self, kind, planes, blocks, expansion, stride, groups=1, residual_block=None):
         out_planes = planes * expansion
         downsample = None
         if stride != 1 or self.inplanes != out_planes:  # models/resnet.py:176-181
@@ -292,10 +311,16 @@ class ResNetImagenet(tnn.Module):
             downsample = tnn.Sequential(
                 Conv(self.inplanes, out_planes, kernel_size=1, stride=stride, bias=False),
                 Norm(out_planes))
-        stage = [ResidualBlock(kind, self.inplanes, planes, stride, expansion, downsample, self.op_classes, groups, self.norm)]
+        if residual_block is not None:
+            # models/resnet.py:182-183: ONE module per stage, constructed (its initial weights drawn) behind the stage's
+            # downsample and before its blocks, and handed to every block
+            residual_block = residual_block(out_planes)
+        stage = [ResidualBlock(kind, self.inplanes, planes, stride, expansion, downsample, self.op_classes, groups, self.norm,
+                               residual_block)]
         self.inplanes = out_planes
         for _ in range(1, blocks):
-            stage.append(ResidualBlock(kind, self.inplanes, planes, 1, expansion, None, self.op_classes, groups, self.norm))
+            stage.append(ResidualBlock(kind, self.inplanes, planes, 1, expansion, None, self.op_classes, groups, self.norm,
+                                       residual_block))
         return tnn.Sequential(*stage)
 
     def features(self, x):
@@ -348,3 +373,15 @@ def resnet(**config):
     if kind == 'basic':
         config['expansion'] = 1
     return ResNetImagenet(**config)
+
+
+def resnet_se(**config):
+    """The reference's resnet_se (models/resnet.py:434-436): resnet(residual_block=SEBlock, **config).  depth and groups as
+    for resnet; quantize=True, bn_norm=... and a non-ImageNet dataset are refused."""
+    if config.get('quantize'):
+        raise NotImplementedError('resnet_se(quantize=True): the gated shortcut is built for the default operators only')
+    if config.get('bn_norm'):
+        raise NotImplementedError('resnet_se(bn_norm=%r): the gated shortcut is built for nn.BatchNorm2d only'
+                                  % (config['bn_norm'],))
+    config['residual_block'] = cnn.SEBlock
+    return resnet(**config)

@@ -287,6 +287,63 @@ class L1BatchNorm2d(_ArenaModule):
         return '{}, eps={}, momentum={}'.format(self.num_features, self.eps, self.momentum)
 
 
+class _SELinear(_ArenaModule):
+    """One dense layer of SEBlock.transform: nn.Linear's parameters, shapes and initial draws; fp32 masters in the arena,
+    read by csrc/se.hip directly (no compute-dtype copy, none of the convolution paths)."""
+
+    def __init__(self, in_features, out_features):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        self.weight = tnn.Parameter(torch.empty(out_features, in_features))
+        init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        self.bias = tnn.Parameter(torch.empty(out_features))
+        bound = 1 / math.sqrt(in_features)
+        init.uniform_(self.bias, -bound, bound)
+
+    def extra_repr(self):
+        return 'in_features={}, out_features={}, bias=True'.format(self.in_features, self.out_features)
+
+
+class SEBlock(tnn.Module):
+    """SEBlock(in_channels, out_channels=None, ratio=16) of the reference (models/modules/se.py:6-25): x * m with
+    m[n, c] = sigmoid(W2 relu(W1 mean_hw(x[n, :, :, c]) + b1) + b2), one operator (ops.SEScaleFunction on csrc/se.hip).
+    The reference's module tree (relu, global_pool, transform = Sequential(Linear, ReLU, Linear, Sigmoid)) gives its
+    state_dict keys and RNG draw order; the sub-modules other than the two dense layers are structure only.  The same in
+    train() and eval().  resnet_se hands ONE instance to every block of a stage: one arena slot per parameter, the
+    gradient summed over the blocks by the kernels."""
+
+    def __init__(self, in_channels, out_channels=None, ratio=16):
+        super().__init__()
+        if out_channels is None:
+            out_channels = in_channels
+        if out_channels != in_channels:
+            raise NotImplementedError('HIP SEBlock gates its own input: out_channels (%d) must equal in_channels (%d)'
+                                      % (out_channels, in_channels))
+        hidden = in_channels // ratio
+        if hidden == 0:
+            raise NotImplementedError('HIP SEBlock(%d, ratio=%d): the hidden layer would have no units (the reference '
+                                      'builds a zero-width Linear)' % (in_channels, ratio))
+        if in_channels > 2048 or hidden > 128:
+            raise NotImplementedError('HIP SEBlock supports up to 2048 channels and 128 hidden units (got %d, %d)'
+                                      % (in_channels, hidden))
+        self.in_channels, self.ratio, self.hidden_channels = in_channels, ratio, hidden
+        self.relu = ReLU(True)
+        self.global_pool = AdaptiveAvgPool2d(1)
+        self.transform = tnn.Sequential(_SELinear(in_channels, hidden), ReLU(inplace=True),
+                                        _SELinear(hidden, out_channels), tnn.Sigmoid())
+        self._pending_bwd = 0      # forward calls of this step whose backward has not run yet (shared by several blocks)
+
+    def forward(self, x):
+        lin1, lin2 = self.transform[0], self.transform[2]
+        lin1._require_prepared()
+        if torch.is_grad_enabled():
+            return ops.SEScaleFunction.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias, self)
+        return ops.se_scale_infer(x, self)
+
+    def extra_repr(self):
+        return '{}, ratio={}'.format(self.in_channels, self.ratio)
+
+
 class ReLU(tnn.Module):
     def __init__(self, inplace=False):
         super().__init__()

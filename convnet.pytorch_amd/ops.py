@@ -243,6 +243,8 @@ def reset_step_state(model):
         m.__dict__.pop('_lazy_a', None)
         if hasattr(m, '_lazy_dy'):
             m._lazy_dy = None
+        if hasattr(m, '_pending_bwd'):
+            m._pending_bwd = 0
     SIDE.reset()
     from . import quant
     quant.reset_step_state()
@@ -1480,6 +1482,102 @@ def l1_batch_norm_infer(y, residual, mod, relu):
                            ptr(mod.bias), ptr(mod.running_mean), ptr(mod.running_var), ptr(coeffs), N * H * W, C,
                            int(relu), dtype_code(y.dtype), stream_of(y))
     return z
+
+
+def _se_shape(r, mod):
+    N, H, W, C = r.shape
+    Cr = mod.hidden_channels
+    if C != mod.in_channels or C % _lib.chunk_elems(r.dtype) != 0:
+        raise _lib.ConvNetHipError('SEBlock(%d) got an NHWC input %s in %s: the channels must match and be a multiple of the '
+                                   'dtype\'s chunk' % (mod.in_channels, tuple(r.shape), r.dtype))
+    return N, H * W, C, Cr
+
+
+def _se_gate(r, mod, N, HW, C, Cr):
+    """squeeze + excite of nn.SEBlock: (s, h, m), all fp32.  The squeeze is csrc/se.hip's own reduction: cn_avgpool_fwd
+    rounds its means to the compute dtype."""
+    L = _L()
+    code = dtype_code(r.dtype)
+    ws = workspace(L.cn_se_workspace(N, HW, C, Cr, code), r.device)
+    s = torch.empty((N, C), dtype=torch.float32, device=r.device)
+    h = torch.empty((N, Cr), dtype=torch.float32, device=r.device)
+    m = torch.empty((N, C), dtype=torch.float32, device=r.device)
+    lin1, lin2 = mod.transform[0], mod.transform[2]
+    PROFILER.run('se_squeeze', 2, 0.0, r.numel() * _esize(r),
+                 lambda: L.cn_se_squeeze(ptr(r), ptr(s), N, HW, C, code, ptr(ws), ws.numel() * 4, stream_of(r)), r.device)
+    PROFILER.run('se_excite_fwd', 1, 4.0 * N * C * Cr, 8.0 * N * C * Cr,
+                 lambda: L.cn_se_excite_fwd(ptr(s), ptr(lin1.master_view('weight')), ptr(lin1.master_view('bias')),
+                                            ptr(lin2.master_view('weight')), ptr(lin2.master_view('bias')), ptr(h), ptr(m),
+                                            N, C, Cr, stream_of(r)), r.device)
+    return s, h, m
+
+
+class SEScaleFunction(Function):
+    """rs = r * m, m = sigmoid(W2 relu(W1 mean_hw(r) + b1) + b2) per sample and channel (nn.SEBlock on csrc/se.hip).
+    forward: squeeze -> excite -> scale; backward: reduce (dm = sum_hw g*r) -> excite backward (ds and the four parameter
+    gradients, accumulated into the arena: a module shared by the blocks of a stage receives their sum) -> apply
+    (dr = g*m + ds/HW).  No host synchronisation, grow-only workspace: capturable."""
+
+    @staticmethod
+    def forward(ctx, r, w1, b1, w2, b2, mod):
+        r = r.contiguous()
+        N, HW, C, Cr = _se_shape(r, mod)
+        s, h, m = _se_gate(r, mod, N, HW, C, Cr)
+        rs = torch.empty_like(r)
+        nb = r.numel() * _esize(r)
+        PROFILER.run('se_scale_fwd', 1, 0.0, 2 * nb,
+                     lambda: _L().cn_se_scale_fwd(ptr(r), ptr(m), ptr(rs), N, HW, C, dtype_code(r.dtype), stream_of(r)),
+                     r.device)
+        COUNTERS['se_fwd'] = COUNTERS.get('se_fwd', 0) + 1
+        ctx.mod = mod
+        ctx.save_for_backward(r, s, h, m)
+        mod._pending_bwd += 1
+        return rs
+
+    @staticmethod
+    def backward(ctx, g):
+        r, s, h, m = ctx.saved_tensors
+        mod = ctx.mod
+        N, HW, C, Cr = _se_shape(r, mod)
+        L = _L()
+        code = dtype_code(r.dtype)
+        g = g.contiguous()
+        ws = workspace(L.cn_se_workspace(N, HW, C, Cr, code), r.device)
+        lin1, lin2 = mod.transform[0], mod.transform[2]
+        dm = torch.empty((N, C), dtype=torch.float32, device=r.device)
+        ds = torch.empty((N, C), dtype=torch.float32, device=r.device)
+        nb = r.numel() * _esize(r)
+        COUNTERS['se_bwd'] = COUNTERS.get('se_bwd', 0) + 1
+        PROFILER.run('se_scale_bwd_reduce', 2, 0.0, 2 * nb,
+                     lambda: L.cn_se_scale_bwd_reduce(ptr(g), ptr(r), ptr(dm), N, HW, C, code, ptr(ws), ws.numel() * 4,
+                                                      stream_of(r)), r.device)
+        PROFILER.run('se_excite_bwd', 2, 8.0 * N * C * Cr, 16.0 * N * C * Cr,
+                     lambda: L.cn_se_excite_bwd(ptr(dm), ptr(s), ptr(h), ptr(m), ptr(lin1.master_view('weight')),
+                                                ptr(lin2.master_view('weight')), ptr(ds), ptr(lin1.grad_view('weight')),
+                                                ptr(lin1.grad_view('bias')), ptr(lin2.grad_view('weight')),
+                                                ptr(lin2.grad_view('bias')), 1.0, 1.0, N, C, Cr, ptr(ws), ws.numel() * 4,
+                                                stream_of(r)), r.device)
+        dr = None
+        if ctx.needs_input_grad[0]:
+            dr = torch.empty_like(r)
+            PROFILER.run('se_scale_bwd_apply', 1, 0.0, 2 * nb,
+                         lambda: L.cn_se_scale_bwd_apply(ptr(g), ptr(m), ptr(ds), None, ptr(dr), N, HW, C, code,
+                                                         stream_of(r)), r.device)
+        mod._pending_bwd -= 1
+        if mod._pending_bwd <= 0:    # the last of the blocks that share this module: its gradients are complete
+            mod._pending_bwd = 0
+            lin1._notify_grad_ready()
+            lin2._notify_grad_ready()
+        return dr, None, None, None, None, None
+
+
+def se_scale_infer(r, mod):
+    r = r.contiguous()
+    N, HW, C, Cr = _se_shape(r, mod)
+    _, _, m = _se_gate(r, mod, N, HW, C, Cr)
+    rs = torch.empty_like(r)
+    _L().cn_se_scale_fwd(ptr(r), ptr(m), ptr(rs), N, HW, C, dtype_code(r.dtype), stream_of(r))
+    return rs
 
 
 class MaxPool2dFunction(Function):

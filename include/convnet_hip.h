@@ -331,6 +331,33 @@ cn_status cn_l1bn_bwd(const void* dz, const void* y, const unsigned char* relu_m
                       float* coef_scratch /*3C*/, int M, int C, int relu, int dtype, void* workspace, size_t ws_bytes,
                       void* stream);
 
+/* ---- SEBlock: squeeze-and-excitation gate on the shortcut of resnet_se (models/modules/se.py:6-25,
+ * models/resnet.py:112-113, 159-160) ---------------------------------------------------------------
+ * r, rs, g, dr, addend: NHWC [N][HW][C] in `dtype`; everything of size N*C or N*Cr is fp32; w1[Cr][C], w2[C][Cr] and the
+ * biases are the fp32 masters.  C a multiple of the chunk, C <= 2048, 1 <= Cr <= 128, N <= 65535.
+ *  cn_se_squeeze            s[n][c] = mean_hw r (fp32 accumulation, never rounded through 16 bits)
+ *  cn_se_excite_fwd         h = relu(w1 s + b1), m = sigmoid(w2 h + b2) per sample
+ *  cn_se_scale_fwd          rs = r * m[n][c]
+ *  cn_se_scale_bwd_reduce   dm[n][c] = sum_hw g*r
+ *  cn_se_excite_bwd         dz2 = dm*m*(1 - m), dh = (w2^T dz2)*[h > 0], ds = w1^T dh; dw2 = sum_n dz2 (x) h, db2 = sum_n dz2,
+ *                           dw1 = sum_n dh (x) s, db1 = sum_n dh, each written as beta*dst + scale*(...)
+ *  cn_se_scale_bwd_apply    dr = g*m[n][c] + ds[n][c]/HW (+ addend, optional), rounded once
+ * No atomics: every reduction has one order (partial rows in the workspace + a fixed-order finalize launch).
+ * cn_se_workspace: bytes that cover every one of these calls at that shape (0: shape not supported). */
+size_t cn_se_workspace(int N, int HW, int C, int Cr, int dtype);
+cn_status cn_se_squeeze(const void* r, float* s, int N, int HW, int C, int dtype, void* workspace, size_t ws_bytes,
+                        void* stream);
+cn_status cn_se_excite_fwd(const float* s, const float* w1, const float* b1, const float* w2, const float* b2, float* h,
+                           float* m, int N, int C, int Cr, void* stream);
+cn_status cn_se_scale_fwd(const void* r, const float* m, void* rs, int N, int HW, int C, int dtype, void* stream);
+cn_status cn_se_scale_bwd_reduce(const void* g, const void* r, float* dm, int N, int HW, int C, int dtype, void* workspace,
+                                 size_t ws_bytes, void* stream);
+cn_status cn_se_excite_bwd(const float* dm, const float* s, const float* h, const float* m, const float* w1, const float* w2,
+                           float* ds, float* dw1, float* db1, float* dw2, float* db2, float beta, float scale, int N, int C,
+                           int Cr, void* workspace, size_t ws_bytes, void* stream);
+cn_status cn_se_scale_bwd_apply(const void* g, const float* m, const float* ds, const void* addend, void* dr, int N, int HW,
+                                int C, int dtype, void* stream);
+
 /* ---- nn.SyncBatchNorm (main.py:190-191, --sync-bn) ----------------------------------------------
  * Each rank reduces its own statistics to 2*C doubles, the caller all-reduces that buffer in-stream
  * (cn_comm_allreduce, dtype 2, on the rank's communicator handle) and passes the global sums and the global row
