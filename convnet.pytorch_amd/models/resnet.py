@@ -23,6 +23,7 @@ import torch
 import torch.nn as tnn
 
 from .. import nn as cnn
+from ..ops import ResGradHolder
 
 __all__ = ['resnet', 'resnet_se']
 
@@ -55,6 +56,14 @@ def weight_decay_config(value=1e-4, log=False):
 def linear_scale(lr0, lrT, T, t0=0):
     rate = (lrT - lr0) / T
     return "lambda t: {'lr': max(%s + (t - %s) * %s, 0)}" % (lr0, t0, rate)
+
+
+def _link_stats(conv, bn):
+    """`bn` behind `conv` with every fusion: its statistics come out of the conv epilogue, centred on its running mean, and its
+    backward apply can be left to the conv (ops.LAZY_DY).  (Instance dict: neither becomes a sub-module of the other.)"""
+    conv.feeds_batchnorm = True
+    conv.__dict__['stats_bn'] = bn
+    bn.__dict__['producer_conv'] = conv
 
 
 class ResidualBlock(tnn.Module):
@@ -93,9 +102,7 @@ class ResidualBlock(tnn.Module):
                                              padding=k // 2, bias=False, **gkw))
             setattr(self, 'bn%d' % i, Norm(cout))
             if not self.quantized and not self.nofuse[i - 1]:
-                getattr(self, 'conv%d' % i).feeds_batchnorm = True   # BN statistics come out of the conv epilogue
-                getattr(self, 'conv%d' % i).__dict__['stats_bn'] = getattr(self, 'bn%d' % i)   # ... centred on its running mean
-                getattr(self, 'bn%d' % i).__dict__['producer_conv'] = getattr(self, 'conv%d' % i)   # (lazy dy: ops.LAZY_DY)
+                _link_stats(getattr(self, 'conv%d' % i), getattr(self, 'bn%d' % i))
             if i > 1 and not self.quantized and not self.nofuse[i - 1] and not self.nofuse[i - 2]:   # this conv reads relu(bn_{i-1}(.)): its dgrad epilogue does that BN's backward reduction
                 # (instance dict, not setattr: the BN must not become a registered sub-module of the conv)
                 getattr(self, 'conv%d' % i).__dict__['input_bn'] = getattr(self, 'bn%d' % (i - 1))
@@ -115,7 +122,6 @@ class ResidualBlock(tnn.Module):
             # the two gradients meeting at the block input are summed in the later data gradient's epilogue
             # (quant.JUNCTION_ADD): conv1 + the identity shortcut's gradient (parked by quant.add_relu), or conv1 + the
             # projection convolution
-            from ..ops import ResGradHolder
             self._holder = ResGradHolder()
             self.conv1._res_holder = self._holder
             if downsample is not None:
@@ -130,12 +136,9 @@ class ResidualBlock(tnn.Module):
             # meeting at the block input are added by the fork
             self._holder = None
             if downsample is not None and not self.unfused_norm:
-                downsample[0].feeds_batchnorm = True
-                downsample[0].__dict__['stats_bn'] = downsample[1]
-                downsample[1].__dict__['producer_conv'] = downsample[0]
+                _link_stats(downsample[0], downsample[1])
             return
         # the two gradients meeting at the block input are summed inside a dgrad epilogue
-        from ..ops import ResGradHolder
         self._holder = ResGradHolder()
         self.conv1._res_holder = self._holder
         self.conv1.__dict__['junction_conv1'] = True   # (never a lazy-dy consumer: ops._lazy_dy_ok)
@@ -143,9 +146,7 @@ class ResidualBlock(tnn.Module):
             self.last_bn()._res_holder = self._holder     # identity: last BN's dres + conv1 dgrad
         else:
             downsample[0]._res_holder = self._holder      # downsample conv dgrad + conv1 dgrad
-            downsample[0].feeds_batchnorm = True
-            downsample[0].__dict__['stats_bn'] = downsample[1]
-            downsample[1].__dict__['producer_conv'] = downsample[0]
+            _link_stats(downsample[0], downsample[1])
 
     def last_bn(self):
         return getattr(self, 'bn%d' % self.n_convs)

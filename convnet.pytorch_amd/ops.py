@@ -10,6 +10,7 @@ pass over tensor data is one of the `cn_*` kernels.
 import collections
 import contextlib
 import os
+import typing
 import weakref
 
 import torch
@@ -239,10 +240,8 @@ def reset_step_state(model):
         h = getattr(m, '_res_holder', None)
         if h is not None:
             h.reset()
-        m.__dict__.pop('_lazy_z', None)
-        m.__dict__.pop('_lazy_a', None)
-        if hasattr(m, '_lazy_dy'):
-            m._lazy_dy = None
+        for slot in _SLOTS + ('_fwd_ctx',):    # (_fwd_ctx: the BatchNorm's weak reference to its forward state)
+            m.__dict__.pop(slot, None)
         if hasattr(m, '_pending_bwd'):
             m._pending_bwd = 0
     SIDE.reset()
@@ -370,6 +369,72 @@ def take_pending_stats(y):
     return ps
 
 
+def _wants_stats(mod):
+    """This convolution's epilogue emits the statistics partials of the BatchNorm behind it (model wiring: feeds_batchnorm)."""
+    return FUSE_BN_STATS and mod.training and getattr(mod, 'feeds_batchnorm', False)
+
+
+# ---- per-step hand-offs between layers: a layer parks a half-finished result on the neighbouring module whose kernel
+# finishes it.  One record per hand-off (plain tuples in positional order: the raw kernel wrappers take any sequence of
+# that length) and ONE mailbox, _park / _take: the record sits in the module's instance dict under the slot's name beside
+# its owner tensor's (address, shape, dtype).  A new per-step hand-off is a record plus a name in _SLOTS.
+_T, _OptT = torch.Tensor, typing.Optional[torch.Tensor]
+# _lazy_z, on the consumer conv: the junction z = relu?(bn(y) + residual) it forms on its operand load and stores
+# (res_stats set: behind a projection shortcut, whose BatchNorm is applied to `residual` here too)
+LazyZ = typing.NamedTuple('LazyZ', [('y', _T), ('residual', _T), ('stats', _T), ('res_stats', _OptT), ('z', _T),
+                                    ('mask', _OptT), ('relu', bool)])
+# _lazy_a, on the consumer conv: the inner BatchNorm output a = relu?(bn(bn_y)) it forms on its operand path and stores
+LazyA = typing.NamedTuple('LazyA', [('bn_y', _T), ('stats', _T), ('a', _T), ('relu', bool)])
+# _lazy_dy, on the producer conv: its upstream gradient dy = c1*g + c2*bn_y + c3, left unformed by the BatchNorm behind it
+LazyDy = typing.NamedTuple('LazyDy', [('g', _T), ('bn_y', _T), ('coef', _T)])
+# _bwd_partials, on the BatchNorm: its backward reduction partials out of the consumer conv's dgrad epilogue
+BwdPartials = typing.NamedTuple('BwdPartials', [('partial', _T), ('rows', int)])
+# _deferred, on the projection shortcut's BatchNorm: finalised statistics that the junction's apply pass applies
+DeferredBN = typing.NamedTuple('DeferredBN', [('stats', _T)])
+# _q_stash, on a quantised block's conv1: the block input's row min / max and quantised copy, for the projection (quant.py)
+QStash = typing.NamedTuple('QStash', [('bits', int), ('mm', _T), ('qx', _T)])
+# conv2d_dgrad's bn= argument: the forward state of the BatchNorm whose backward reduction the epilogue does
+BnBwdOperands = typing.NamedTuple('BnBwdOperands', [('y', _T), ('mask', _OptT), ('stats', _T), ('relu', bool)])
+_SLOTS = ('_lazy_z', '_lazy_a', '_lazy_dy', '_bwd_partials', '_deferred', '_q_stash')
+# what a strict _take raises for an entry that belongs to another tensor (the other slots' takers fall back silently)
+_MISMATCH = {'_lazy_z': 'lazy z: the parked junction is not this convolution\'s input',
+             '_lazy_a': 'lazy a: the parked BatchNorm output is not this convolution\'s input',
+             '_lazy_dy': 'lazy dy: the parked gradient does not belong to this convolution\'s output '
+                         '(stale mailbox entry or a second consumer)',
+             '_deferred': 'deferred shortcut BatchNorm met a junction that cannot apply it'}
+
+
+def _owner_key(t):
+    return t.data_ptr(), tuple(t.shape), t.dtype
+
+
+def _park(mod, slot, owner, record):
+    """Leave `record` on `mod` for the operator that will hold the tensor `owner`."""
+    if slot not in _SLOTS:
+        raise _lib.ConvNetHipError('unknown per-step mailbox slot %r' % (slot,))
+    mod.__dict__[slot] = (_owner_key(owner), record)
+
+
+def _take(mod, slot, owner=None, strict=True):
+    """The record parked in `slot` (taken: a second call returns None).  owner: the tensor - or its _owner_key - the entry
+    must have been parked for; an entry of another tensor raises the slot's message when strict, else it is dropped."""
+    entry = mod.__dict__.pop(slot, None)
+    if entry is None:
+        return None
+    if owner is not None and entry[0] != (owner if isinstance(owner, tuple) else _owner_key(owner)):
+        if strict:
+            raise _lib.ConvNetHipError(_MISMATCH[slot])
+        return None
+    return entry[1]
+
+
+def _refuse_parked(mod, who):
+    """For an operator that takes part in no fusion: whatever was parked on its module is an error."""
+    for slot in _SLOTS:
+        if mod.__dict__.get(slot) is not None:
+            raise _lib.ConvNetHipError('%s: a %s hand-off was parked for it (it takes part in no fusion)' % (who, slot[1:]))
+
+
 def stats_pivot(conv_mod):
     """The running mean of the BatchNorm that consumes this convolution's output (wired by the model as
     conv.stats_bn): the pivot of the centred statistics the epilogue emits.  None: plain sums."""
@@ -444,7 +509,7 @@ def conv2d_fwd(x, w_krsc, bias, K, R, S, stride, pad, out_f32=False, relu=False,
 def conv2d_fwd_lazyz(lz, w_krsc, K, bn_stats=False, pivot=None):
     """conv1x1(z) with z = relu(bn(y) + residual) formed on the operand load and stored by the kernel
     (cn_conv2d_fwd_lazyz).  lz: the junction's parked state (BatchNormActFunction.forward)."""
-    y3, res, stats, res_stats, z, mask, relu = lz
+    y3, res, stats, res_stats, z, mask, relu = LazyZ(*lz)
     N, H, W, C = y3.shape
     out = torch.empty((N, H, W, K), dtype=y3.dtype, device=y3.device)
     L = _L()
@@ -489,7 +554,7 @@ def lazy_a_consumer_ok(conv, y):
 def conv2d_fwd_lazya(la, w_krsc, K, bn_stats=False, kernel=(1, 1)):
     """la = (bn_y, stats, a, relu) parked by BatchNormActFunction: y = conv(relu?(bn_y * scale + shift)), a written
     (1x1: the streaming kernel; 3x3: the 64-channel halo kernel)."""
-    bn_y, stats, a, relu = la
+    bn_y, stats, a, relu = LazyA(*la)
     N, H, W, C = bn_y.shape
     L = _L()
     y = torch.empty((N, H, W, K), dtype=bn_y.dtype, device=bn_y.device)
@@ -548,7 +613,7 @@ def conv2d_dgrad(dy, w_crsk, x_shape, K, R, S, stride, pad, addend=None, bn=None
                                                      dtype_code(dy.dtype), 0, stream_of(dy)),
                      dy.device, detail=detail)
         return dx
-    bn_y, bn_mask, bn_stats, bn_relu = bn
+    bn_y, bn_mask, bn_stats, bn_relu = BnBwdOperands(*bn)
     L = _L()
     if JDGRAD and (R, S) == (1, 1) and tuple(stride) == (1, 1) and tuple(pad) == (0, 0) and bn_mask is not None \
             and addend is not None and L.cn_conv2d_dgrad_junction_ok(C, K, dtype_code(dy.dtype)):
@@ -844,7 +909,7 @@ def fill_f32_(x, v=0.0):
 # bucket manager start the all-reduce of a finished bucket while backward continues.
 
 def _input_bn_state(conv_mod, x):
-    """(bn module, y, mask, stats, relu) of the BatchNorm whose output *is* the convolution input `x`
+    """(bn module, BnBwdOperands) of the BatchNorm whose output *is* the convolution input `x`
     (wired by the model as conv.input_bn), when that BatchNorm's forward state is still alive and
     belongs to this very tensor; else None."""
     bn_mod = getattr(conv_mod, 'input_bn', None)
@@ -866,7 +931,7 @@ def _input_bn_state(conv_mod, x):
         return None
     if y.shape[-1] % _lib.chunk_elems(y.dtype) != 0:
         return None
-    return bn_mod, y, mask, stats, bctx.relu
+    return bn_mod, BnBwdOperands(y, mask, stats, bctx.relu)
 
 
 _ZEROS = {}
@@ -903,69 +968,58 @@ class Conv2dFunction(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, mod):
         mod.ensure_prepared()
-        lz = mod.__dict__.pop('_lazy_z', None)
+        lz, la = _take(mod, '_lazy_z', x), _take(mod, '_lazy_a', x)
+        if bias is not None and (lz is not None or la is not None):
+            raise _lib.ConvNetHipError(_MISMATCH['_lazy_z' if lz is not None else '_lazy_a'])
         if lz is not None:    # x is a junction output that exists only as (y, residual, statistics): this kernel writes it
-            if lz[0] != x.data_ptr() or bias is not None:
-                raise _lib.ConvNetHipError('lazy z: the parked junction is not this convolution\'s input')
-            y = conv2d_fwd_lazyz(lz[1:], mod.w_krsc, mod.out_channels,
-                                 bn_stats=FUSE_BN_STATS and mod.training and getattr(mod, 'feeds_batchnorm', False),
-                                 pivot=stats_pivot(mod))
+            y = conv2d_fwd_lazyz(lz, mod.w_krsc, mod.out_channels, bn_stats=_wants_stats(mod), pivot=stats_pivot(mod))
             COUNTERS['lazy_z'] = COUNTERS.get('lazy_z', 0) + 1
-        elif mod.__dict__.get('_lazy_a') is not None:   # x is an inner BatchNorm's output that exists only as (y, statistics)
-            la = mod.__dict__.pop('_lazy_a')
-            if la[0] != x.data_ptr() or bias is not None:
-                raise _lib.ConvNetHipError('lazy a: the parked BatchNorm output is not this convolution\'s input')
-            y = conv2d_fwd_lazya(la[1:], mod.w_krsc, mod.out_channels,
-                                 bn_stats=FUSE_BN_STATS and mod.training and getattr(mod, 'feeds_batchnorm', False),
-                                 kernel=mod.kernel_size)
+        elif la is not None:   # x is an inner BatchNorm's output that exists only as (y, statistics)
+            y = conv2d_fwd_lazya(la, mod.w_krsc, mod.out_channels, bn_stats=_wants_stats(mod), kernel=mod.kernel_size)
             COUNTERS['lazy_a'] = COUNTERS.get('lazy_a', 0) + 1
         else:
             y = conv2d_fwd(x, mod.w_krsc, bias, mod.out_channels, mod.kernel_size[0], mod.kernel_size[1],
-                           mod.stride, mod.padding, out_f32=mod.out_f32,
-                           bn_stats=FUSE_BN_STATS and mod.training and getattr(mod, 'feeds_batchnorm', False),
+                           mod.stride, mod.padding, out_f32=mod.out_f32, bn_stats=_wants_stats(mod),
                            pivot=stats_pivot(mod))
         ctx.mod = mod
         ctx.has_bias = bias is not None
         ctx.save_for_backward(x)
         # the lazy-dy mailbox is matched against THIS output in backward; an entry left by an aborted backward dies here
-        ctx.out_ptr, ctx.out_shape = y.data_ptr(), tuple(y.shape)
-        mod._lazy_dy = None
+        ctx.out_key = _owner_key(y)
+        _take(mod, '_lazy_dy')
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         mod = ctx.mod
-        lazy = getattr(mod, '_lazy_dy', None)     # (g, bn_y, coef): the BatchNorm behind this conv left dy unformed
-        mod._lazy_dy = None
+        lazy = _take(mod, '_lazy_dy', ctx.out_key)     # the BatchNorm behind this conv left dy unformed
+        holder = getattr(mod, '_res_holder', None)
         R, S = mod.kernel_size
         if lazy is None and _is_zero_placeholder(dy):
             raise _lib.ConvNetHipError('lazy dy: the gradient placeholder reached a convolution with an empty mailbox '
                                        '(the BatchNorm that parked the gradient is not this convolution\'s consumer)')
         if lazy is not None:
             g, bn_y, coef = lazy
-            if bn_y.data_ptr() != ctx.out_ptr or tuple(bn_y.shape) != ctx.out_shape or tuple(g.shape) != tuple(dy.shape):
-                raise _lib.ConvNetHipError('lazy dy: the parked gradient does not belong to this convolution\'s output '
-                                           '(stale mailbox entry or a second consumer)')
+            if tuple(g.shape) != tuple(dy.shape):
+                raise _lib.ConvNetHipError(_MISMATCH['_lazy_dy'])
             if JPAIR and (R, S) == (1, 1) and mod.stride == (1, 1) and mod.padding == (0, 0) and ctx.needs_input_grad[0] \
                     and mod.in_channels == x.shape[-1] \
                     and _L().cn_conv2d_bwd1x1_lazy_ok(x.shape[-1], mod.out_channels, dtype_code(x.dtype)):
                 # junction pair: both gradients of this convolution in one pass over (g, bn_y), on the backward chain
-                holder = getattr(mod, '_res_holder', None)
                 if holder is not None and holder.dres is not None:
                     raise _lib.ConvNetHipError('lazy dy met a fused-addend dgrad: the junction layout changed')
                 dx = conv2d_bwd1x1_lazy(x, g, bn_y, coef, mod.w_crsk, mod.grad_view('weight'), mod.out_channels)
                 mod._notify_grad_ready()
                 COUNTERS['jpair'] = COUNTERS.get('jpair', 0) + 1
                 if holder is not None:
-                    holder.dres, holder.sub, holder.fused = dx, 1, False
+                    holder.park(dx)
                 return dx, None, None, None
             _submit_wgrad(mod, lambda tag: conv2d_wgrad_lazy(x, g, bn_y, coef, mod.grad_view('weight'), mod.in_channels,
                                                              mod.out_channels, R, S, mod.stride, mod.padding, tag=tag),
                           (x, g, bn_y, coef), coef)
             if not ctx.needs_input_grad[0]:
                 return None, None, None, None
-            holder = getattr(mod, '_res_holder', None)
             if holder is not None and holder.dres is not None:
                 raise _lib.ConvNetHipError('lazy dy met a fused-addend dgrad: the junction layout changed')
             if holder is not None and SUBSAMPLED_SHORTCUT_GRAD and (R, S) == (1, 1) and mod.stride == (2, 2) \
@@ -973,11 +1027,11 @@ class Conv2dFunction(Function):
                 N_, H_, W_, C_ = x.shape
                 compact = conv2d_dgrad_lazy(g, bn_y, coef, mod.w_crsk, (N_, (H_ + 1) // 2, (W_ + 1) // 2, C_),
                                             mod.out_channels, 1, 1, (1, 1), (0, 0))
-                holder.dres, holder.sub, holder.fused = compact, 2, False
+                holder.park(compact, 2)
                 return _zero_like_placeholder(x), None, None, None
             dx = conv2d_dgrad_lazy(g, bn_y, coef, mod.w_crsk, x.shape, mod.out_channels, R, S, mod.stride, mod.padding)
             if holder is not None:
-                holder.dres, holder.sub, holder.fused = dx, 1, False
+                holder.park(dx)
             return dx, None, None, None
         dy = dy.contiguous()
         if dy.dtype != x.dtype:  # fp32 logits gradient -> compute dtype
@@ -993,12 +1047,10 @@ class Conv2dFunction(Function):
             dx = None
             if ctx.needs_input_grad[0]:
                 addend, addend_sub = None, 1
-                holder = getattr(mod, '_res_holder', None)
                 if holder is not None and holder.dres is not None and holder.dres.dtype == dy.dtype \
                         and (holder.dres.shape == x.shape if holder.sub == 1 else
                              tuple(holder.dres.shape) == (x.shape[0], (x.shape[1] + 1) // 2, (x.shape[2] + 1) // 2, x.shape[3])):
-                    addend, addend_sub = holder.dres, holder.sub   # the other branch's gradient, folded into this dgrad epilogue
-                    holder.fused = True
+                    addend, addend_sub = holder.claim()   # the other branch's gradient, folded into this dgrad epilogue
                 elif holder is not None and holder.dres is None and SUBSAMPLED_SHORTCUT_GRAD \
                         and (R, S) == (1, 1) and mod.stride == (2, 2) and mod.padding == (0, 0):
                     # stride-2 1x1 projection shortcut, first of the two gradients that meet at the block input: its input
@@ -1007,7 +1059,7 @@ class Conv2dFunction(Function):
                     N_, H_, W_, C_ = x.shape
                     compact = conv2d_dgrad(dy, mod.w_crsk, (N_, (H_ + 1) // 2, (W_ + 1) // 2, C_), mod.out_channels, 1, 1,
                                            (1, 1), (0, 0))
-                    holder.dres, holder.sub, holder.fused = compact, 2, False
+                    holder.park(compact, 2)
                     return _zero_like_placeholder(x), None, None, None
                 # this dgrad is the last contribution to the gradient of x when x has no other consumer
                 # (inner convs) or when the other branch's gradient is being added right here
@@ -1016,17 +1068,15 @@ class Conv2dFunction(Function):
                 if bn_args is not None and holder is None:
                     bn_args = None      # junctions only (see FUSE_BN_BWD)
                 if bn_args is not None:
-                    bn_mod, bn_y, bn_mask, bn_stats, bn_relu = bn_args
+                    bn_mod, bn = bn_args
                     dx, partial, rows = conv2d_dgrad(dy, mod.w_crsk, x.shape, mod.out_channels, R, S, mod.stride,
-                                                     mod.padding, addend=addend, bn=(bn_y, bn_mask, bn_stats, bn_relu),
-                                                     addend_sub=addend_sub)
-                    bn_mod._bwd_partials = (dx.data_ptr(), tuple(dx.shape), partial, rows)
+                                                     mod.padding, addend=addend, bn=bn, addend_sub=addend_sub)
+                    _park(bn_mod, '_bwd_partials', dx, BwdPartials(partial, rows))
                 else:
                     dx = conv2d_dgrad(dy, mod.w_crsk, x.shape, mod.out_channels, R, S, mod.stride, mod.padding,
                                       addend=addend, addend_sub=addend_sub)
                 if holder is not None and addend is None:
-                    holder.dres, holder.sub = dx, 1   # first producer of the fork gradient: park it for the other
-                    holder.fused = False
+                    holder.park(dx)   # first producer of the fork gradient: park it for the other
             return dx, None, None, None
 
         # The data gradient is the backward chain's next kernel; the weight gradient only has to start some time.  Launching
@@ -1049,12 +1099,10 @@ class GroupedConv2dFunction(Function):
     @staticmethod
     def forward(ctx, x, weight, mod):
         mod.ensure_prepared()
-        if mod.__dict__.get('_lazy_z') is not None or mod.__dict__.get('_lazy_a') is not None:
-            raise _lib.ConvNetHipError('grouped convolution: a lazy operand was parked for it (grouped convs take no fusion)')
+        _refuse_parked(mod, 'grouped convolution')
         y = gconv2d_fwd(x, mod.w_krsc, mod.out_channels, mod.groups, mod.stride[0])
         ctx.mod = mod
         ctx.save_for_backward(x)
-        mod._lazy_dy = None
         COUNTERS['gconv'] = COUNTERS.get('gconv', 0) + 1
         return y
 
@@ -1062,7 +1110,8 @@ class GroupedConv2dFunction(Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         mod = ctx.mod
-        if getattr(mod, '_lazy_dy', None) is not None or _is_zero_placeholder(dy):
+        _refuse_parked(mod, 'grouped convolution')
+        if _is_zero_placeholder(dy):
             raise _lib.ConvNetHipError('grouped convolution: a lazy gradient reached it (grouped convs take no fusion)')
         dy = dy.contiguous()
         K, g, st = mod.out_channels, mod.groups, mod.stride[0]
@@ -1113,7 +1162,7 @@ class StemPairConvFunction(Function):
         wp = torch.empty(K * R * S2 * 8, dtype=torch.bfloat16, device=x_pairs.device)
         L.cn_weight_prep_pairs(ptr(mod.master_view('weight')), ptr(wp), K, R, S, mod.in_channels,
                                stream_of(x_pairs))
-        want_stats = FUSE_BN_STATS and mod.training and getattr(mod, 'feeds_batchnorm', False)
+        want_stats = _wants_stats(mod)
         N_, Hp_, Jp_, _ = x_pairs.shape
         if STEM_HALO and want_stats and stats_pivot(mod) is None and mod.stride[0] == 2 and x_pairs.dtype == torch.bfloat16 \
                 and L.cn_stem_fwd_ok(K, R, S2, Jp_, dtype_code(x_pairs.dtype)):
@@ -1203,13 +1252,12 @@ class BatchNormActFunction(Function):
         # res_bn: `residual` is that BatchNorm's deferred input
         dual = None
         if res_bn is not None:
-            d = getattr(res_bn, '_deferred', None)
-            res_bn._deferred = None
-            if d is not None and residual is not None and d[0] == residual.data_ptr() and _sync_group(mod) is None \
+            d = _take(res_bn, '_deferred', residual)
+            if d is not None and residual is not None and _sync_group(mod) is None \
                     and tuple(residual.shape) == tuple(y.shape) and residual.dtype == y.dtype:
-                dual = d[1]
+                dual = d.stats
             elif d is not None:
-                raise _lib.ConvNetHipError('deferred shortcut BatchNorm met a junction that cannot apply it')
+                raise _lib.ConvNetHipError(_MISMATCH['_deferred'])
         z = None if defer else torch.empty_like(y)
         # lazy z: the junction is finalised here and applied by the 1x1 convolution that consumes it (LAZY_Z)
         cons = getattr(mod, 'consumer_conv', None)
@@ -1268,9 +1316,9 @@ class BatchNormActFunction(Function):
                              ptr(ws), ws.numel() * 4, stream_of(y)),
                          y.device)
         if lazyz:
-            cons.__dict__['_lazy_z'] = (z.data_ptr(), y, residual.contiguous(), stats, dual, z, mask, relu)
+            _park(cons, '_lazy_z', z, LazyZ(y, residual.contiguous(), stats, dual, z, mask, relu))
         elif lazya:
-            icons.__dict__['_lazy_a'] = (z.data_ptr(), y, stats, z, relu)
+            _park(icons, '_lazy_a', z, LazyA(y, stats, z, relu))
         elif dual is not None:    # both BatchNorms finalised: one apply pass reads y and the shortcut's raw input
             PROFILER.run('bn_apply (junction + projection-shortcut BatchNorm)', 1, 0.0,
                          nb * 3 + (mask.numel() if mask is not None else 0),
@@ -1288,7 +1336,7 @@ class BatchNormActFunction(Function):
         else:
             ctx.save_for_backward(y, stats)
         if defer:
-            mod._deferred = (y.data_ptr(), stats)
+            _park(mod, '_deferred', y, DeferredBN(stats))
             return y     # (autograd hands back an alias of the input: same storage, this node as its grad_fn)
         return z
 
@@ -1308,15 +1356,14 @@ class BatchNormActFunction(Function):
         want_res = ctx.has_res and ctx.needs_input_grad[3]
         coef = torch.empty(3 * C, dtype=torch.float32, device=y.device)
         nb = y.numel() * _esize(y)
-        pp = getattr(mod, '_bwd_partials', None)
-        mod._bwd_partials = None
-        fused_in = pp is not None and pp[0] == dz.data_ptr() and pp[1] == tuple(dz.shape) and dz.dtype == y.dtype
+        pp = _take(mod, '_bwd_partials', dz, strict=False)   # (another tensor's entry: not fused, the plain passes run)
+        fused_in = pp is not None and dz.dtype == y.dtype
         if ctx.sync is not None:
             group, world = ctx.sync
             COUNTERS['bn_bwd_fused' if fused_in else 'bn_bwd_plain'] += 1
             local = torch.empty(2 * C, dtype=torch.float64, device=y.device)
             L.cn_bn_bwd_local_sums(ptr(dz), ptr(y), ptr(zmask), ptr(stats), M, C, int(ctx.relu), code,
-                                   ptr(pp[2]) if fused_in else None, pp[3] if fused_in else 0, ptr(local),
+                                   ptr(pp.partial) if fused_in else None, pp.rows if fused_in else 0, ptr(local),
                                    ptr(ws), ws.numel() * 4, stream_of(y))
             glob = local.clone()
             _sync_all_reduce(glob, group, world)
@@ -1331,7 +1378,7 @@ class BatchNormActFunction(Function):
         elif fused_in and _lazy_dy_ok(mod, y):
             # ... and the apply pass is left to the consumers: finalize only, dy = c1*g + c2*y + c3 is formed on the
             # operand loads of the producing convolution's dgrad / wgrad (see LAZY_DY)
-            _, _, partial, rows = pp
+            partial, rows = pp
             COUNTERS['bn_bwd_fused'] += 1
             COUNTERS['bn_bwd_lazy'] = COUNTERS.get('bn_bwd_lazy', 0) + 1
             dres = dz if want_res else None
@@ -1342,11 +1389,11 @@ class BatchNormActFunction(Function):
                                                           1.0, 1.0, ptr(coef), M, C, code, ptr(partial), rows,
                                                           ptr(ws), ws.numel() * 4, stream_of(y)),
                              y.device)
-            mod.producer_conv._lazy_dy = (dz, y, coef)
+            _park(mod.producer_conv, '_lazy_dy', y, LazyDy(dz, y, coef))
             dy = _zero_like_placeholder(y)
         elif fused_in:
             # dz arrived masked (g) with its reduction partials from the producing dgrad's epilogue
-            _, _, partial, rows = pp
+            partial, rows = pp
             COUNTERS['bn_bwd_fused'] += 1
             dres = dz if want_res else None       # the residual branch's gradient is g itself
             with SIDE.mark(dy):
@@ -1370,7 +1417,7 @@ class BatchNormActFunction(Function):
                                                  1.0, 1.0, ptr(coef), M, C, 0, code, ptr(ws),
                                                  ws.numel() * 4, stream_of(y)),
                              y.device)
-            mod.producer_conv._lazy_dy = (dz, y, coef)
+            _park(mod.producer_conv, '_lazy_dy', y, LazyDy(dz, y, coef))
             dy = _zero_like_placeholder(y)
         else:
             COUNTERS['bn_bwd_plain'] += 1
@@ -1386,8 +1433,7 @@ class BatchNormActFunction(Function):
         mod._notify_grad_ready()
         holder = getattr(mod, '_res_holder', None)
         if holder is not None:
-            holder.dres, holder.sub = dres, 1
-            holder.fused = False
+            holder.park(dres)
         return dy, None, None, dres, None, None, None, None
 
 
@@ -1793,12 +1839,7 @@ class ForkFunction(Function):
 
     @staticmethod
     def backward(ctx, ga, gb):
-        holder = ctx.holder
-        fused = holder is not None and holder.fused
-        first = holder.dres if holder is not None else None
-        sub = holder.sub if holder is not None else 1
-        if holder is not None:
-            holder.dres, holder.fused, holder.sub = None, False, 1
+        first, sub, fused = ctx.holder.take() if ctx.holder is not None else (None, 1, False)
         if sub == 2 and not fused and first is not None:
             # a subsampled projection-shortcut gradient that no dgrad epilogue picked up (not the case in the ResNet
             # blocks: conv1 always does): scatter it into a dense tensor here (data movement only) and add
@@ -1828,6 +1869,18 @@ class ResGradHolder(object):
 
     def reset(self):
         self.dres, self.fused, self.sub = None, False, 1
+
+    def park(self, t, sub=1):     # the first of the two gradients
+        self.dres, self.sub, self.fused = t, sub, False
+
+    def claim(self):              # (dres, sub) for the second branch's dgrad epilogue: the fork then passes that sum on
+        self.fused = True
+        return self.dres, self.sub
+
+    def take(self):               # (dres, sub, fused) at the fork's backward; the holder is empty again
+        out = (self.dres, self.sub, self.fused)
+        self.reset()
+        return out
 
 
 class SoftmaxCrossEntropyFunction(Function):

@@ -60,7 +60,7 @@ _MM_STASH = {}
 
 
 def reset_step_state():
-    """Drop what an aborted step stashed (ops.reset_step_state)."""
+    """Drop what an aborted step stashed (ops.reset_step_state; the modules' _q_stash goes with its loop over ops._SLOTS)."""
     _MM_STASH.clear()
 
 
@@ -387,19 +387,19 @@ class QConv2dFunction(Function):
             # updates its own running range (identical values)
             qm = mod.quantize_input
             src = getattr(mod, 'share_q_from', None)
-            st = src.__dict__.pop('_q_stash', None) if src is not None else None
             x = x.contiguous()
-            if st is not None and qm.training and st[0] == x.data_ptr() and st[1] == tuple(x.shape) \
-                    and st[2] == qm.num_bits:
-                qparams(st[3], x.shape[0], 0, qm.running_zero_point, qm.running_range, qm.momentum)
-                qx = st[4]
+            # (ops.QStash; another tensor's entry or another bit width: this convolution quantises x itself)
+            st = ops._take(src, '_q_stash', x, strict=False) if src is not None else None
+            if st is not None and qm.training and st.bits == qm.num_bits:
+                qparams(st.mm, x.shape[0], 0, qm.running_zero_point, qm.running_range, qm.momentum)
+                qx = st.qx
             elif qm.training and getattr(mod, 'share_q_out', False):
                 # (QuantMeasure exists in ONE configuration - its constructor refuses stochastic / non-dequantising /
                 # other flatten_dims - so the shared copy depends on num_bits only, which the stash records and matches)
                 mm = minmax_rows(x, x.shape[0])
                 qp = qparams(mm, x.shape[0], 0, qm.running_zero_point, qm.running_range, qm.momentum)
                 qx = quantize(x, qp[0:1], qp[1:2], qm.num_bits)
-                mod.__dict__['_q_stash'] = (x.data_ptr(), tuple(x.shape), qm.num_bits, mm, qx)
+                ops._park(mod, '_q_stash', x, ops.QStash(qm.num_bits, mm, qx))
             else:
                 qx = qm(x)
         _quantize_filters(mod, mod.num_bits_weight)
@@ -440,11 +440,11 @@ class QConv2dFunction(Function):
             addend = None
             if holder is not None and holder.dres is not None and holder.sub == 1 and holder.dres.dtype == gq.dtype \
                     and tuple(holder.dres.shape) == tuple(qx.shape):
-                addend, holder.fused = holder.dres, True
+                addend, _ = holder.claim()
             dx = ops.conv2d_dgrad(gq, mod.w_crsk, qx.shape, mod.out_channels, R, S, mod.stride, mod.padding,
                                   addend=addend)
             if holder is not None and addend is None:
-                holder.dres, holder.sub, holder.fused = dx, 1, False
+                holder.park(dx)
         return dx, None, None, None
 
 
@@ -739,7 +739,7 @@ class AddReLUFunction(Function):
             _L().cn_eltwise(2, ptr(g), ptr(dz), ptr(z), dz.numel(), dtype_code(dz.dtype), stream_of(dz))
         if ctx.holder is not None and JUNCTION_ADD:
             # identity shortcut: g IS the shortcut branch's gradient at the block input; conv1's data gradient adds it
-            ctx.holder.dres, ctx.holder.sub, ctx.holder.fused = g, 1, False
+            ctx.holder.park(g)
         return g, g, None, None
 
 
