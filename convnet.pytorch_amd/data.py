@@ -102,6 +102,64 @@ class CenterCrop(object):
         return 'CenterCrop(%d)' % self.size
 
 
+class RandomCrop(object):
+    """torchvision.transforms.RandomCrop(size, padding): the image is padded with 0 on every side FIRST, then the corner is
+    drawn as torchvision's get_params does - torch.randint(0, h - th + 1, (1,)) for the top, then torch.randint(0, w - tw + 1,
+    (1,)) for the left; no draw when the padded image already has the crop's size."""
+
+    def __init__(self, size, padding=None):
+        self.size, self.padding = int(size), int(padding or 0)
+
+    def get_params(self, w, h):
+        th = tw = self.size
+        if h < th or w < tw:
+            raise ValueError('RandomCrop(%d): the (padded) image is %d x %d' % (self.size, h, w))
+        if w == tw and h == th:
+            return 0, 0
+        top = torch.randint(0, h - th + 1, size=(1,)).item()
+        left = torch.randint(0, w - tw + 1, size=(1,)).item()
+        return top, left
+
+    def __call__(self, img):
+        if self.padding > 0:
+            w, h = img.size
+            canvas = _pil().new(img.mode, (w + 2 * self.padding, h + 2 * self.padding))     # (fill 0)
+            canvas.paste(img, (self.padding, self.padding))
+            img = canvas
+        top, left = self.get_params(*img.size)
+        return img.crop((left, top, left + self.size, top + self.size))
+
+    def __repr__(self):
+        return 'RandomCrop(%d, padding=%d)' % (self.size, self.padding)
+
+
+def cutout_rect(y, x, length, h, w):
+    """preprocess.Cutout's rectangle around the centre (y, x), clipped to the image: (y1, y2, x1, x2)."""
+    half = length // 2
+    return (int(np.clip(y - half, 0, h)), int(np.clip(y + half, 0, h)), int(np.clip(x - half, 0, w)),
+            int(np.clip(x + half, 0, w)))
+
+
+class Cutout(object):
+    """preprocess.Cutout (preprocess.py:185-227): `holes` square patches of side `length` set to 0 in the NORMALISED CHW
+    tensor, centres drawn with np.random.randint(h), np.random.randint(w) as the reference does."""
+
+    def __init__(self, holes, length):
+        self.holes, self.length = int(holes), int(length)
+
+    def __call__(self, img):
+        out = img.clone()
+        rows, cols = out.shape[1], out.shape[2]
+        for _ in range(self.holes):      # (row centre first, then column centre: the reference's order of draws)
+            centre = (np.random.randint(rows), np.random.randint(cols))
+            y1, y2, x1, x2 = cutout_rect(centre[0], centre[1], self.length, rows, cols)
+            out[:, y1:y2, x1:x2] = 0
+        return out
+
+    def __repr__(self):
+        return 'Cutout(holes=%d, length=%d)' % (self.holes, self.length)
+
+
 class RandomResizedCrop(object):
     """Inception-style crop: area fraction in `scale`, aspect ratio log-uniform in `ratio`, ten
     attempts then a centre crop clamped to the ratio range; resized to size x size (bilinear)."""
@@ -460,9 +518,13 @@ def get_transform(transform_name='imagenet', input_size=None, scale_size=None, n
                   cutout=None, autoaugment=False, padding=None, duplicates=1, num_crops=1, device_normalize=False,
                   device_resize=False):
     """preprocess.get_transform (preprocess.py:115-161) for the ImageNet family, `duplicates` (multi_transform) included;
-    the other research augmentations (autoaugment, cutout, multi-crop) are outside the hot path."""
+    the other research augmentations (autoaugment, cutout, multi-crop) are outside the hot path.  'cifar...': the
+    reference's random_crop / scale_crop branch (:133-147) with Cutout, on the host (the device-resident path is
+    DeviceCifarLoader)."""
+    if 'cifar' in transform_name:
+        return _cifar_transform(input_size, scale_size, normalize, augment, cutout, autoaugment, padding, duplicates, num_crops)
     if 'imagenet' not in transform_name:
-        raise NotImplementedError('transform %r: only the ImageNet pipeline is built' % transform_name)
+        raise NotImplementedError('transform %r: the ImageNet and CIFAR pipelines are built' % transform_name)
     if autoaugment or cutout is not None or num_crops != 1:
         raise NotImplementedError('autoaugment / cutout / multi-crop are not part of the hot path')
     duplicates = int(duplicates)
@@ -490,6 +552,32 @@ def get_transform(transform_name='imagenet', input_size=None, scale_size=None, n
     else:
         one = scale_crop(input_size=input_size, scale_size=scale_size, normalize=normalize, device_normalize=device_normalize,
                          device_resize=device_resize)
+    return one if duplicates == 1 else MultiTransform(one, duplicates)
+
+
+def _cifar_transform(input_size, scale_size, normalize, augment, cutout, autoaugment, padding, duplicates, num_crops):
+    """preprocess.py:133-147, 159-161.  train: RandomCrop(32, padding=4) -> RandomHorizontalFlip -> ToTensor -> Normalize (the
+    ImageNet statistics are the reference's default here too); eval: CenterCrop(32) -> ToTensor -> Normalize; cutout appends
+    Cutout to either; duplicates goes through MultiTransform."""
+    if autoaugment:
+        raise NotImplementedError('autoaugment (CIFAR10Policy) is not built')
+    if num_crops != 1:
+        raise NotImplementedError('multi-crop evaluation is not built')
+    duplicates = int(duplicates)
+    if duplicates < 1:
+        raise ValueError('duplicates must be >= 1, got %d' % duplicates)
+    normalize = normalize or _IMAGENET_STATS
+    input_size = input_size or 32
+    scale_size = scale_size or 32
+    if scale_size != input_size:
+        raise NotImplementedError('cifar transform with a Resize step (scale_size %d != input_size %d)' % (scale_size, input_size))
+    if augment:
+        t = [RandomCrop(scale_size, padding=padding or 4), RandomHorizontalFlip(), ToTensor(), Normalize(**normalize)]
+    else:
+        t = [CenterCrop(input_size), ToTensor(), Normalize(**normalize)]
+    if cutout is not None:
+        t.append(Cutout(**cutout))
+    one = Compose(t)
     return one if duplicates == 1 else MultiTransform(one, duplicates)
 
 
@@ -537,13 +625,175 @@ class ImageFolder(Dataset):
         return img, target
 
 
+class CIFAR(Dataset):
+    """torchvision.datasets.CIFAR10 / CIFAR100 as data.get_dataset uses them (data.py:23-40), from the python-pickle
+    releases in LOCAL files only:
+        <root>/cifar-10-batches-py/{data_batch_1..5, test_batch}    keys data (uint8 [n, 3072], planar CHW), labels
+        <root>/cifar-100-python/{train, test}                       keys data, fine_labels
+    `data` is uint8 [N, 32, 32, 3] (HWC), `targets` a list of ints.  `download` is accepted and ignored: nothing here
+    fetches anything; a missing file raises FileNotFoundError naming it."""
+    LAYOUT = {10: ('cifar-10-batches-py', ['data_batch_%d' % i for i in range(1, 6)], ['test_batch'], 'labels'),
+              100: ('cifar-100-python', ['train'], ['test'], 'fine_labels')}
+
+    def __init__(self, root, classes=10, train=True, transform=None, target_transform=None, download=False):
+        import pickle
+        folder, train_files, test_files, key = self.LAYOUT[classes]
+        self.root, self.train, self.num_classes = os.path.expanduser(root), train, classes
+        self.transform, self.target_transform = transform, target_transform
+        data, self.targets = [], []
+        for name in (train_files if train else test_files):
+            path = os.path.join(self.root, folder, name)
+            if not os.path.isfile(path):
+                raise FileNotFoundError('CIFAR-%d file %r does not exist (datasets are read from local files only)'
+                                        % (classes, path))
+            with open(path, 'rb') as f:
+                entry = pickle.load(f, encoding='latin1')
+            data.append(np.asarray(entry['data'], dtype=np.uint8).reshape(-1, 3, 32, 32))
+            self.targets.extend(int(t) for t in entry[key])
+        self.data = np.ascontiguousarray(np.concatenate(data).transpose(0, 2, 3, 1))      # planar CHW -> HWC
+        if len(self.targets) != self.data.shape[0]:
+            raise ValueError('CIFAR-%d: %d images but %d labels' % (classes, self.data.shape[0], len(self.targets)))
+
+    def __len__(self):
+        return self.data.shape[0]
+
+    def __getitem__(self, i):
+        img, target = _pil().fromarray(self.data[i]), self.targets[i]
+        if self.transform is not None:
+            img = self.transform(img)
+        if self.target_transform is not None:
+            target = self.target_transform(target)
+        return img, target
+
+
 def get_dataset(name, split='train', transform=None, target_transform=None, download=True,
                 datasets_path='~/Datasets'):
-    """data.get_dataset (data.py:17-70) for `imagenet`: <datasets_path>/imagenet/{train,val}/<class>/*."""
+    """data.get_dataset (data.py:17-70) for `imagenet`: <datasets_path>/imagenet/{train,val}/<class>/*; `cifar10` /
+    `cifar100`: <datasets_path>/<name>/ holding the extracted python release (CIFAR)."""
+    if name in ('cifar10', 'cifar100'):
+        return CIFAR(os.path.join(os.path.expanduser(datasets_path), name), classes=int(name[5:]), train=split == 'train',
+                     transform=transform, target_transform=target_transform, download=download)
     if name != 'imagenet':
-        raise NotImplementedError('dataset %r: the folder pipeline is built for "imagenet"' % name)
+        raise NotImplementedError('dataset %r: the pipelines built are "imagenet" (folders), "cifar10" and "cifar100"' % name)
     root = os.path.join(os.path.expanduser(datasets_path), name, 'train' if split == 'train' else 'val')
     return ImageFolder(root, transform=transform, target_transform=target_transform)
+
+
+class DeviceCifarLoader(object):
+    """A CIFAR split resident in device memory (uint8 HWC, 150 MB for all of CIFAR-10) and one kernel per batch
+    (ops.crop_flip_normalize, csrc/augment.hip) that cuts the batch out of it: iterating yields (inputs, target) already on
+    the device, inputs in the NHWC compute-dtype form conv1 reads ([B, S, S, c_pad], or [B, D, S, S, c_pad] for duplicates
+    = D > 1, sample-major).
+    train (augment): a torch.randperm per epoch and drop_last; per batch the crop corners, flips and cutout centres are drawn
+    VECTORISED on the host (draw_params: torch's global generator for crop / flip, numpy's for cutout, like the reference's
+    transforms - the same distributions, not the per-sample draw order of the worker pipeline) and travel with the indices
+    as one small pinned copy.  Copy and kernel are queued on the CURRENT stream, in front of the step that reads the batch
+    (the kernel is tens of microseconds: a stream of its own would buy nothing).  eval: sequential, identity crop, partial
+    last batch.
+    distributed: the epoch permutation is seeded with the epoch and sharded rank::world, as DistributedSampler does."""
+
+    def __init__(self, dataset, batch_size, device, dtype=torch.float32, augment=True, padding=4, cutout=None, duplicates=1,
+                 normalize=None, shuffle=None, drop_last=None, distributed=False, rank=None, world_size=None, seed=0):
+        from . import _lib, ops
+        self.device, self.dtype = torch.device(device), dtype
+        self.batch_size, self.augment, self.duplicates = int(batch_size), bool(augment), int(duplicates)
+        self.pad = int(padding or 4) if self.augment else 0
+        if cutout is not None and int(cutout.get('holes', 1)) != 1:
+            raise NotImplementedError('DeviceCifarLoader: one cutout hole per image (the kernel takes one rectangle)')
+        self.cutout = cutout
+        self.shuffle = self.augment if shuffle is None else bool(shuffle)
+        self.drop_last = self.augment if drop_last is None else bool(drop_last)
+        if self.batch_size < 1 or self.duplicates < 1:
+            raise ValueError('batch_size and duplicates must be >= 1')
+        data = torch.from_numpy(np.ascontiguousarray(dataset.data))
+        self.N, self.S = data.shape[0], data.shape[1]
+        self.rank, self.world = 0, 1
+        if distributed:
+            import torch.distributed as dist
+            self.rank = dist.get_rank() if rank is None else int(rank)
+            self.world = dist.get_world_size() if world_size is None else int(world_size)
+        self.distributed, self.seed, self.epoch = bool(distributed), int(seed), 0
+        self.data = data.to(self.device)
+        self.targets = torch.tensor(dataset.targets, dtype=torch.int64).to(self.device)
+        self.lut = ops.normalize_lut(**(normalize or _IMAGENET_STATS)).to(self.device)
+        self._ops, self._lib = ops, _lib
+        self.device_normalize = None        # (trainer.DevicePrefetcher: these batches are final)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def _n_local(self):
+        if not self.distributed:
+            return self.N
+        return (self.N + self.world - 1) // self.world        # DistributedSampler pads to equal shards
+
+    def __len__(self):
+        n = self._n_local()
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def epoch_indices(self):
+        """This rank's sample order for the current epoch (int64, host)."""
+        if self.distributed:
+            if self.shuffle:
+                g = torch.Generator().manual_seed(self.seed + self.epoch)
+                order = torch.randperm(self.N, generator=g)
+            else:
+                order = torch.arange(self.N)
+            total = self._n_local() * self.world
+            if total > self.N:
+                order = torch.cat([order, order[:total - self.N]])
+            return order[self.rank:total:self.world]
+        return torch.randperm(self.N) if self.shuffle else torch.arange(self.N)
+
+    def draw_params(self, B, D=1, pad=None, cutout=None):
+        """int32 [B * D, ops.AUGMENT_PARAMS] records (top, left, flip, y1, y2, x1, x2, 0) for B samples x D views, drawn in
+        three vectorised calls: torch.randint for the corners, torch.rand for the flips (torch's global generator) and
+        np.random.randint for the cutout centres (numpy's global generator)."""
+        pad = self.pad if pad is None else int(pad)
+        V, S = B * D, self.S
+        p = torch.zeros((V, self._ops.AUGMENT_PARAMS), dtype=torch.int32)
+        if pad > 0:
+            p[:, 0:2] = torch.randint(0, 2 * pad + 1, (V, 2), dtype=torch.int32)
+        p[:, 2] = (torch.rand(V) < 0.5).to(torch.int32)
+        if cutout is not None:
+            half = int(cutout['length']) // 2
+            c = torch.from_numpy(np.random.randint(S, size=(V, 2)).astype(np.int32))
+            p[:, 3] = (c[:, 0] - half).clamp_(0, S)
+            p[:, 4] = (c[:, 0] + half).clamp_(0, S)
+            p[:, 5] = (c[:, 1] - half).clamp_(0, S)
+            p[:, 6] = (c[:, 1] + half).clamp_(0, S)
+        return p
+
+    def batch(self, index):
+        """(inputs, target) on the device for the samples `index` (int64, host)."""
+        B, D = index.shape[0], self.duplicates
+        V = B * D
+        NP = self._ops.AUGMENT_PARAMS
+        rec = torch.empty(V * (1 + NP), dtype=torch.int32, pin_memory=self.device.type == 'cuda')
+        h_idx, h_params = rec[:V], rec[V:].view(V, NP)
+        h_idx.copy_(index.repeat_interleave(D) if D > 1 else index)
+        if self.augment:
+            h_params.copy_(self.draw_params(B, D, self.pad, self.cutout))
+        else:
+            h_params.zero_()
+        if self.device.type == 'cuda':
+            d_rec = rec.to(self.device, non_blocking=True)
+            d_idx, d_params = d_rec[:V], d_rec[V:].view(V, NP)
+            x = self._ops.crop_flip_normalize(self.data, d_idx, d_params, self.lut, self.dtype, 'nhwc', pad=self.pad,
+                                              host=(h_idx, h_params))
+            target = self.targets.index_select(0, d_idx[::D].to(torch.int64))
+        else:
+            x = self._ops.crop_flip_normalize(self.data, h_idx, h_params, self.lut, self.dtype, 'nhwc', pad=self.pad)
+            target = self.targets.index_select(0, index)
+        if D > 1:
+            x = x.view(B, D, *x.shape[1:])
+        return x, target
+
+    def __iter__(self):
+        order = self.epoch_indices()
+        bs = self.batch_size
+        for i in range(len(self)):
+            yield self.batch(order[i * bs:(i + 1) * bs])
 
 
 _DATA_ARGS = {'name', 'split', 'transform', 'target_transform', 'download', 'datasets_path'}
@@ -551,7 +801,7 @@ _DATALOADER_ARGS = {'batch_size', 'shuffle', 'sampler', 'batch_sampler', 'num_wo
                     'drop_last', 'timeout', 'worker_init_fn'}
 _TRANSFORM_ARGS = {'transform_name', 'input_size', 'scale_size', 'normalize', 'augment', 'cutout', 'duplicates',
                    'num_crops', 'autoaugment', 'device_normalize', 'device_resize'}
-_OTHER_ARGS = {'distributed'}
+_OTHER_ARGS = {'distributed', 'device', 'dtype'}
 
 
 def _seed_worker(worker_id):
@@ -588,6 +838,11 @@ class DataRegime(object):
             setting = self.get_setting()
             if override_settings is not None:
                 setting.update(override_settings)
+            if 'cifar' in setting['data']['name'] and setting['transform'].get('device_normalize'):
+                return self._device_cifar_loader(setting)
+            if 'cifar' in setting['data']['name']:      # (the worker pipeline: fp32 batches from the host transforms)
+                for k in ('device_normalize', 'device_resize'):
+                    setting['transform'].pop(k, None)
             self._transform = get_transform(**setting['transform'])
             setting['data'].setdefault('transform', self._transform)
             self._data = get_dataset(**setting['data'])
@@ -608,6 +863,22 @@ class DataRegime(object):
             # uint8 HWC batches carry what the device-side ToTensor + Normalize needs (trainer.DevicePrefetcher reads it)
             self._loader.device_normalize = dict(setting['transform'].get('normalize') or _IMAGENET_STATS) \
                 if setting['transform'].get('device_normalize') else None
+        return self._loader
+
+    def _device_cifar_loader(self, setting):
+        """A cifar dataset under device_normalize: the split lives in device memory (DeviceCifarLoader)."""
+        t, other, loader = setting['transform'], setting['other'], setting['loader']
+        if t.get('autoaugment'):
+            raise NotImplementedError('autoaugment (CIFAR10Policy) is not built')
+        if other.get('device') is None:
+            raise ValueError("a device-resident cifar regime needs the engine's device in its defaults ('device')")
+        self._data = get_dataset(**setting['data'])
+        self._sampler = self._loader = DeviceCifarLoader(
+            self._data, loader.get('batch_size', 1), other['device'], other.get('dtype') or torch.float32,
+            augment=t.get('augment', True), padding=t.get('padding'), cutout=t.get('cutout'),
+            duplicates=int(t.get('duplicates', 1) or 1), normalize=t.get('normalize'), shuffle=bool(loader.get('shuffle')),
+            drop_last=bool(loader.get('drop_last')), distributed=bool(other.get('distributed', False)))
+        self._loader.set_epoch(self.epoch)
         return self._loader
 
     def set_epoch(self, epoch):

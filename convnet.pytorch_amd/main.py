@@ -12,7 +12,9 @@ re-authored for the MI355X engine:
   optim_state_dict, best_prec1); `state_dict` tensors have the reference's OIHW shapes, so
   checkpoints load both ways;
 * data: a synthetic ImageNet-shaped dataset (`--dataset imagenet-synthetic`, the default here);
-  `--dataset imagenet --datasets-dir ...` drives the image-folder pipeline of data.py.
+  `--dataset imagenet --datasets-dir ...` drives the image-folder pipeline of data.py; `--dataset cifar10 | cifar100` the
+  CIFAR pickles (resident in device memory unless --host-normalize), `cifar10-synthetic | cifar100-synthetic` CIFAR-shaped
+  synthetic batches.
 """
 import argparse
 import csv
@@ -271,8 +273,11 @@ def main_worker(args):
     args.eval_batch_size = args.eval_batch_size if args.eval_batch_size > 0 else args.batch_size
     if 'synthetic' in args.dataset:
         is_mnist = args.model == 'mnist'
-        size = args.input_size or (28 if is_mnist else 224)
-        classes, channels = (10, 1) if is_mnist else (model_config.get('num_classes', 1000), 3)
+        # cifar10-synthetic / cifar100-synthetic: CIFAR-shaped batches (32 x 32, 10 / 100 classes) without data files
+        is_cifar = 'cifar' in args.dataset
+        size = args.input_size or (28 if is_mnist else 32 if is_cifar else 224)
+        default_classes = (100 if 'cifar100' in args.dataset else 10) if is_cifar else 1000
+        classes, channels = (10, 1) if is_mnist else (model_config.get('num_classes', default_classes), 3)
         rank = max(args.local_rank, 0)
         val_data = SyntheticLoader(args.val_steps, args.eval_batch_size, size, classes, channels, args.seed + 10000,
                                    duplicates=args.duplicates if args.evaluate else 1)
@@ -286,8 +291,10 @@ def main_worker(args):
         from .data import DataRegime
         if hasattr(model, 'sampled_data_regime'):
             raise NotImplementedError('sampled (mixed-size) data regimes are not part of the hot path')
+        # (a cifar dataset under device_normalize lives in device memory, data.DeviceCifarLoader: it needs the engine's device)
+        resident = {'device': device, 'dtype': dtype} if 'cifar' in args.dataset else {}
         val_data = DataRegime(getattr(model, 'data_eval_regime', None),
-                              defaults={'datasets_path': args.datasets_dir, 'name': args.dataset, 'split': 'val',
+                              defaults={'datasets_path': args.datasets_dir, 'name': args.dataset, 'split': 'val', **resident,
                                         # (evaluate.py:181-182: --augment / --duplicates shape the validation loader of an
                                         # --evaluate run; a training run validates on single centre crops, main.py:266)
                                         'augment': bool(args.evaluate and args.augment),
@@ -300,7 +307,7 @@ def main_worker(args):
         val_loader = val_data.get_loader
         if not args.evaluate:
             train_data = DataRegime(getattr(model, 'data_regime', None),
-                                    defaults={'datasets_path': args.datasets_dir, 'name': args.dataset,
+                                    defaults={'datasets_path': args.datasets_dir, 'name': args.dataset, **resident,
                                               'split': 'train', 'augment': True, 'input_size': args.input_size,
                                               'batch_size': args.batch_size, 'shuffle': True,
                                               'num_workers': args.workers, 'pin_memory': True, 'drop_last': True,

@@ -1,4 +1,4 @@
-"""ResNet family (ImageNet variant) on the HIP operator modules.
+"""ResNet family (ImageNet and CIFAR variants) on the HIP operator modules.
 
 Same factory surface, module tree / ``state_dict`` keys, initialisation and optimisation regimes
 as /root/reference models/resnet.py (factory :385-431, ResNet_imagenet :216-317, blocks :81-165,
@@ -11,8 +11,11 @@ builds the same tree with ``nn.L1BatchNorm2d`` (csrc/l1bn.hip) for the stem, bra
 part in no convolution-epilogue fusion.  ``resnet_se`` (:434-436 there: resnet(residual_block=SEBlock)) constructs ONE
 ``nn.SEBlock`` (csrc/se.hip) per stage, hands that same module to every block of the stage and applies it to the SHORTCUT
 (z = relu(bn_last(y) + se(r)), r the block input or the shortcut BatchNorm's output); every fusion that rests on the
-junction reading the untouched block input is off in such a model.  Out of scope here (not reachable from the BASELINE
-configs): ResNet_cifar, mixed-size "sampled" regimes, checkpoint_segments, bn_norm='TopK'.
+junction reading the untouched block input is off in such a model.  ``resnet(dataset='cifar10' | 'cifar100')`` is the
+reference's ResNet_cifar (:320-383, factory :423-431): a 3x3 / stride 1 stem without max-pool, three stages of basic blocks
+(depth = 6n + 2, default 44) at widths 16 / 32 / 64, its two regimes, and ``dropout=p`` behind the first ReLU of every
+block; it is built for the default operators only (no quantize / bn_norm / residual_block / groups, no mixup, no "sampled"
+regime).  Out of scope here: mixed-size "sampled" regimes, mixup layers, checkpoint_segments, bn_norm='TopK'.
 
 Module construction order and registration order deliberately match the reference, so seeding
 torch's RNG and building ``resnet(depth=50)`` yields bit-identical initial weights.
@@ -71,9 +74,15 @@ class ResidualBlock(tnn.Module):
     The last BN of the branch fuses `+ residual` and the final ReLU; inner BNs fuse their ReLU."""
 
     def __init__(self, kind, inplanes, planes, stride, expansion, downsample, op_classes=None, groups=1, norm=None,
-                 residual_block=None):
+                 residual_block=None, dropout=None):
         super().__init__()
         self.kind = kind
+        # dropout = p > 0 (ResNet_cifar's blocks): Dropout(p) sits between relu(bn_i(.)) and conv_{i+1}, so that BatchNorm
+        # applies its ReLU itself and hands over a materialised tensor, and conv_{i+1} - which reads the dropped tensor, not
+        # the BatchNorm's output - does none of that BatchNorm's work: no input_bn, no inner_consumer_conv in this block
+        self.drop_p = float(dropout or 0)
+        if self.drop_p and (op_classes is not None or kind != 'basic'):
+            raise NotImplementedError('dropout inside a residual block is built for the basic block of the default operators')
         # residual_block (resnet_se: the stage's shared nn.SEBlock) gates the shortcut before the junction.  The junction
         # then no longer reads the untouched block input, so everything resting on that is off: no ResGradHolder (the
         # fork adds the two block-input gradients), no junction_conv1, no input_bn / consumer_conv across the block
@@ -103,7 +112,7 @@ class ResidualBlock(tnn.Module):
             setattr(self, 'bn%d' % i, Norm(cout))
             if not self.quantized and not self.nofuse[i - 1]:
                 _link_stats(getattr(self, 'conv%d' % i), getattr(self, 'bn%d' % i))
-            if i > 1 and not self.quantized and not self.nofuse[i - 1] and not self.nofuse[i - 2]:   # this conv reads relu(bn_{i-1}(.)): its dgrad epilogue does that BN's backward reduction
+            if i > 1 and not self.quantized and not self.nofuse[i - 1] and not self.nofuse[i - 2] and not self.drop_p:   # this conv reads relu(bn_{i-1}(.)): its dgrad epilogue does that BN's backward reduction
                 # (instance dict, not setattr: the BN must not become a registered sub-module of the conv)
                 getattr(self, 'conv%d' % i).__dict__['input_bn'] = getattr(self, 'bn%d' % (i - 1))
             if i == 1 and kind == 'basic':
@@ -115,7 +124,7 @@ class ResidualBlock(tnn.Module):
         self.downsample = downsample
         self.residual_block = residual_block    # (registered behind downsample, as in the reference's blocks)
         if kind == 'basic':
-            self.dropout = cnn.Dropout(0)
+            self.dropout = cnn.Dropout(self.drop_p)
         self.stride = stride
         self.expansion = expansion
         if self.quantized:   # the reference's operator chain; what is shared / fused is listed in quant.py
@@ -154,7 +163,7 @@ class ResidualBlock(tnn.Module):
     def link_inner_consumers(self):
         """bn_i -> relu -> conv_{i+1} run back to back in forward(): a 1x1 convolution on the streaming kernel / a 3x3
         convolution on the 64-channel halo kernel applies that BatchNorm on its operand path (ops.LAZY_A)."""
-        if not self.quantized:
+        if not self.quantized and not self.drop_p:
             for i in range(1, self.n_convs):
                 if self.nofuse[i - 1] or self.nofuse[i]:
                     continue
@@ -178,6 +187,8 @@ class ResidualBlock(tnn.Module):
         for i in range(1, self.n_convs):
             out = getattr(self, 'conv%d' % i)(out)
             out = getattr(self, 'bn%d' % i)(out, relu=True)
+            if self.drop_p:
+                out = self.dropout(out)
         out = getattr(self, 'conv%d' % self.n_convs)(out)
         residual = xb
         if self.quantized:   # bn -> (downsample) -> add -> relu as separate operators, in the reference's order
@@ -217,7 +228,49 @@ def init_model(model):
     model.fc.bias.data.zero_()
 
 
-class ResNetImagenet(tnn.Module):
+class _ResNetBase(tnn.Module):
+    """What the ImageNet and the CIFAR model share: the operator classes in force, the stage builder and forward()."""
+
+    def __init__(self, op_classes=None, norm=None):
+        super().__init__()
+        self.op_classes = op_classes     # (QConv2d, RangeBN, QLinear) under quantize, else None
+        self.norm = norm                 # nn.L1BatchNorm2d under bn_norm='L1'; None: nn.BatchNorm2d with every fusion
+
+    def _link_blocks(self, first_input_bn=None):
+        """Registration order = execution order of the residual blocks: each block learns which BatchNorm made its input."""
+        prev_bn = first_input_bn
+        for m in self.modules():
+            if isinstance(m, ResidualBlock):
+                if prev_bn is not None:
+                    m.set_input_bn(prev_bn)
+                m.link_inner_consumers()
+                prev_bn = m.last_bn()
+
+    def forward(self, x):
+        return self.fc(self.features(x))
+
+    def _make_layer(self, kind, planes, blocks, expansion, stride, groups=1, residual_block=None, dropout=None):
+        out_planes = planes * expansion
+        downsample = None
+        if stride != 1 or self.inplanes != out_planes:  # models/resnet.py:176-181
+            Conv, Norm = (self.op_classes or (cnn.Conv2d, self.norm or cnn.BatchNorm2d))[:2]
+            downsample = tnn.Sequential(
+                Conv(self.inplanes, out_planes, kernel_size=1, stride=stride, bias=False),
+                Norm(out_planes))
+        if residual_block is not None:
+            # models/resnet.py:182-183: ONE module per stage, constructed (its initial weights drawn) behind the stage's
+            # downsample and before its blocks, and handed to every block
+            residual_block = residual_block(out_planes)
+        stage = [ResidualBlock(kind, self.inplanes, planes, stride, expansion, downsample, self.op_classes, groups, self.norm,
+                               residual_block, dropout)]
+        self.inplanes = out_planes
+        for _ in range(1, blocks):
+            stage.append(ResidualBlock(kind, self.inplanes, planes, 1, expansion, None, self.op_classes, groups, self.norm,
+                                       residual_block, dropout))
+        return tnn.Sequential(*stage)
+
+
+class ResNetImagenet(_ResNetBase):
     num_train_images = 1281167
 
     def __init__(self, num_classes=1000, inplanes=64, block='bottleneck', layers=(3, 4, 23, 3),
@@ -257,13 +310,7 @@ class ResNetImagenet(tnn.Module):
             setattr(self, 'layer%d' % (i + 1),
                     self._make_layer(block, width[i], nblocks, expansion, stride=1 if i == 0 else 2, groups=groups[i],
                                      residual_block=residual_block))
-        prev = None
-        for m in self.modules():   # registration order = execution order of the residual blocks
-            if isinstance(m, ResidualBlock):
-                if prev is not None:
-                    m.set_input_bn(prev.last_bn())
-                m.link_inner_consumers()
-                prev = m
+        self._link_blocks()
         self.avgpool = cnn.AdaptiveAvgPool2d(1)
         self.fc = Dense(width[-1] * expansion, num_classes)
         init_model(self)
@@ -304,26 +351,6 @@ class ResNetImagenet(tnn.Module):
             self.regime[0]['step_lambda'] = linear_scale(0.1, 0.1 * scale_lr, ramp_up_steps)
             self.regime.insert(1, {'epoch': ramp_up_epochs, 'lr': scale_lr * 1e-1})
 
-    def _make_layer(self, kind, planes, blocks, expansion, stride, groups=1, residual_block=None):
-        out_planes = planes * expansion
-        downsample = None
-        if stride != 1 or self.inplanes != out_planes:  # models/resnet.py:176-181
-            Conv, Norm = (self.op_classes or (cnn.Conv2d, self.norm or cnn.BatchNorm2d))[:2]
-            downsample = tnn.Sequential(
-                Conv(self.inplanes, out_planes, kernel_size=1, stride=stride, bias=False),
-                Norm(out_planes))
-        if residual_block is not None:
-            # models/resnet.py:182-183: ONE module per stage, constructed (its initial weights drawn) behind the stage's
-            # downsample and before its blocks, and handed to every block
-            residual_block = residual_block(out_planes)
-        stage = [ResidualBlock(kind, self.inplanes, planes, stride, expansion, downsample, self.op_classes, groups, self.norm,
-                               residual_block)]
-        self.inplanes = out_planes
-        for _ in range(1, blocks):
-            stage.append(ResidualBlock(kind, self.inplanes, planes, 1, expansion, None, self.op_classes, groups, self.norm,
-                                       residual_block))
-        return tnn.Sequential(*stage)
-
     def features(self, x):
         """x: fp32 NCHW (the loader layout) or an already-converted NHWC compute tensor."""
         if self.op_classes is not None and self.training:
@@ -346,8 +373,68 @@ class ResNetImagenet(tnn.Module):
         x = self.avgpool(x)
         return x.view(x.size(0), -1)
 
-    def forward(self, x):
-        return self.fc(self.features(x))
+
+class ResNetCifar(_ResNetBase):
+    """ResNet_cifar of the reference (models/resnet.py:320-383): conv3x3(3, inplanes) / stride 1 -> bn1 + ReLU, no max-pool,
+    three stages of n = (depth - 2) // 6 basic blocks (strides 1, 2, 2; a projection shortcut where the stride is not 1 or the
+    width changes), global average pool, Linear(width[-1], num_classes).  Same construction / registration order, so a seeded
+    build draws the reference's initial tensors."""
+
+    def __init__(self, num_classes=10, inplanes=16, depth=18, width=(16, 32, 64), regime='normal', dropout=None):
+        super().__init__()
+        if 'sampled' in regime:
+            raise NotImplementedError("resnet(dataset='cifar...', regime=%r): mixed-size \"sampled\" data regimes (and their "
+                                      "GradSmooth regulariser) are not built" % (regime,))
+        if len(width) != 3:
+            raise ValueError('a CIFAR ResNet has three stages: width must give three values, got %r' % (width,))
+        n = int((depth - 2) / 6)
+        if n < 1:
+            raise ValueError('unsupported CIFAR ResNet depth %r (depth = 6n + 2, n >= 1)' % (depth,))
+        self.inplanes = inplanes
+        self.conv1 = cnn.Conv2d(3, inplanes, kernel_size=3, stride=1, padding=1, bias=False)
+        self.conv1.needs_dgrad = False  # network input needs no gradient
+        self.bn1 = cnn.BatchNorm2d(inplanes)
+        _link_stats(self.conv1, self.bn1)
+        self.relu = cnn.ReLU(inplace=True)
+        for i in range(3):
+            setattr(self, 'layer%d' % (i + 1),
+                    self._make_layer('basic', width[i], n, 1, stride=1 if i == 0 else 2, dropout=dropout))
+        # (the first block reads relu(bn1(.)) of the stem: a BatchNorm output like any block junction's)
+        self._link_blocks(first_input_bn=self.bn1)
+        self.avgpool = cnn.AdaptiveAvgPool2d(1)
+        self.fc = cnn.Linear(width[-1], num_classes)
+        init_model(self)
+        self.regime = [
+            {'epoch': 0, 'optimizer': 'SGD', 'lr': 1e-1, 'momentum': 0.9, 'regularizer': weight_decay_config(1e-4)},
+            {'epoch': 81, 'lr': 1e-2},
+            {'epoch': 122, 'lr': 1e-3},
+            {'epoch': 164, 'lr': 1e-4},
+        ]
+        if 'wide-resnet' in regime:
+            self.regime = [
+                {'epoch': 0, 'optimizer': 'SGD', 'lr': 1e-1, 'momentum': 0.9, 'regularizer': weight_decay_config(5e-4)},
+                {'epoch': 60, 'lr': 2e-2},
+                {'epoch': 120, 'lr': 4e-3},
+                {'epoch': 160, 'lr': 8e-4},
+            ]
+
+    def features(self, x):
+        """x: fp32 NCHW (the loader layout) or an already-converted NHWC compute tensor (data.DeviceCifarLoader's)."""
+        if x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.shape[-1] != self.conv1.padded_in_channels():
+            x = self.conv1.forward_from_nchw(x)
+        else:
+            x = self.conv1(x)
+        x = self.bn1(x, relu=True)
+        from .. import ops
+        ops.LAZY_Z_SCOPE[0] += 1
+        try:
+            x = self.layer1(x)
+            x = self.layer2(x)
+            x = self.layer3(x)
+        finally:
+            ops.LAZY_Z_SCOPE[0] -= 1
+        x = self.avgpool(x)
+        return x.view(x.size(0), -1)
 
 
 def resnet(**config):
@@ -363,8 +450,10 @@ def resnet(**config):
         raise ValueError("bn_norm must be None or 'L1', got %r" % (bn_norm,))
     config['bn_norm'] = bn_norm
     config['quantize'] = bool(config.pop('quantize', False))
+    if 'cifar10' in dataset:       # ('cifar100' contains 'cifar10'; 'cifar10-synthetic' names the same model)
+        return _resnet_cifar(dataset, config)
     if 'imagenet' not in dataset:
-        raise NotImplementedError("only the ImageNet ResNet variant is built natively (dataset=%r)" % dataset)
+        raise NotImplementedError("the ImageNet and CIFAR ResNet variants are built natively (dataset=%r)" % dataset)
     config.setdefault('num_classes', 1000)
     depth = config.pop('depth', 50)
     if depth not in _IMAGENET_DEPTHS:
@@ -374,6 +463,24 @@ def resnet(**config):
     if kind == 'basic':
         config['expansion'] = 1
     return ResNetImagenet(**config)
+
+
+def _resnet_cifar(dataset, config):
+    """models/resnet.py:423-431: 10 / 100 classes, depth 44.  What the reference would build from the remaining options is
+    refused by name: none of them has CIFAR-sized kernels or a fixture here."""
+    for key, why in (('quantize', 'the quantised operators are built and measured for the ImageNet model only'),
+                     ('bn_norm', 'the L1 norm is wired into the ImageNet model only'),
+                     ('residual_block', 'the gated shortcut (resnet_se) is built for the ImageNet model only'),
+                     ('mixup', "the reference's MixUp layers are not built")):
+        if config.pop(key, None):
+            raise NotImplementedError("resnet(dataset=%r, %s=...): %s" % (dataset, key, why))
+    groups = config.pop('groups', None)
+    if groups is not None and any(int(g) != 1 for g in groups):
+        raise NotImplementedError('resnet(dataset=%r, groups=%r): grouped convolutions are built for the ImageNet model '
+                                  '(ResNeXt) only' % (dataset, groups))
+    config.setdefault('num_classes', 100 if 'cifar100' in dataset else 10)
+    config.setdefault('depth', 44)
+    return ResNetCifar(**config)
 
 
 def resnet_se(**config):

@@ -863,6 +863,70 @@ def u8_nhwc_to_nchw(x_u8, lut):
     return y
 
 
+AUGMENT_PARAMS = 8      # == CN_AUGMENT_PARAMS of include/convnet_hip.h: top, left, flip, y1, y2, x1, x2, 0
+
+
+def check_crop_params(idx, params, N, S, pad):
+    """Range check of a crop_flip_normalize batch on its HOST copies (idx int32 [V], params int32 [V, AUGMENT_PARAMS]):
+    raises before anything is uploaded or launched."""
+    if idx.is_cuda or params.is_cuda:
+        raise _lib.ConvNetHipError('crop_flip_normalize: idx / params are checked on their host copies')
+    if idx.dtype != torch.int32 or params.dtype != torch.int32 or idx.dim() != 1 or params.dim() != 2 \
+            or params.shape[0] != idx.shape[0] or params.shape[1] != AUGMENT_PARAMS or idx.shape[0] == 0:
+        raise _lib.ConvNetHipError('crop_flip_normalize: idx must be int32 [V] and params int32 [V, %d], got %s %s / %s %s'
+                                   % (AUGMENT_PARAMS, idx.dtype, tuple(idx.shape), params.dtype, tuple(params.shape)))
+    if int(idx.min()) < 0 or int(idx.max()) >= N:
+        raise _lib.ConvNetHipError('crop_flip_normalize: idx out of range [0, %d)' % N)
+    top_left, flip = params[:, 0:2], params[:, 2]
+    if int(top_left.min()) < 0 or int(top_left.max()) > 2 * pad:
+        raise _lib.ConvNetHipError('crop_flip_normalize: params out of range: top / left must lie in [0, %d]' % (2 * pad))
+    if int(flip.min()) < 0 or int(flip.max()) > 1:
+        raise _lib.ConvNetHipError('crop_flip_normalize: params out of range: flip must be 0 or 1')
+    rect = params[:, 3:7]
+    if int(rect.min()) < 0 or int(rect.max()) > S or bool((rect[:, 0] > rect[:, 1]).any()) or bool((rect[:, 2] > rect[:, 3]).any()):
+        raise _lib.ConvNetHipError('crop_flip_normalize: params out of range: the cutout rectangle must be clipped to '
+                                   '[0, %d] with y1 <= y2, x1 <= x2' % S)
+
+
+def crop_flip_normalize(data, idx, params, lut, dtype=torch.float32, form='nchw', pad=4, host=None):
+    """RandomCrop(S, padding=pad) -> RandomHorizontalFlip -> ToTensor -> Normalize -> Cutout of the reference's CIFAR
+    pipeline on a dataset resident in device memory (cn_augment_crop_flip): data uint8 [N, S, S, 3], one view per entry
+    of idx / params.  form 'nchw': the loader's fp32 [V, 3, S, S] batch, equal to the host pipeline value for value;
+    form 'nhwc': [V, S, S, c_pad] in `dtype` with zero pad channels, the bits nchw_to_nhwc makes of the former.
+    idx / params are host tensors (checked here, then uploaded); `host` = (idx, params) in host memory when the
+    caller has already uploaded them (the loader: one pinned copy on its own stream)."""
+    if data.dtype != torch.uint8 or data.dim() != 4 or data.shape[1] != data.shape[2] or data.shape[3] != 3:
+        raise _lib.ConvNetHipError('crop_flip_normalize expects uint8 [N, S, S, 3] data, got %s %s' % (data.dtype, tuple(data.shape)))
+    if form not in ('nchw', 'nhwc'):
+        raise ValueError("crop_flip_normalize: form must be 'nchw' or 'nhwc', got %r" % (form,))
+    if form == 'nchw' and dtype != torch.float32:
+        raise _lib.ConvNetHipError('crop_flip_normalize: the nchw form is float32 (the loader batch), got %s' % dtype)
+    code = dtype_code(dtype)
+    _lib.require_device(data, 'data')
+    N, S = data.shape[0], data.shape[1]
+    pad = int(pad)
+    if pad < 0 or pad > S:
+        raise _lib.ConvNetHipError('crop_flip_normalize: pad %d for %d x %d images' % (pad, S, S))
+    if tuple(lut.shape) != (3, 256):
+        raise _lib.ConvNetHipError('crop_flip_normalize: lut %s, expected (3, 256)' % (tuple(lut.shape),))
+    h_idx, h_params = (idx, params) if host is None else host
+    check_crop_params(h_idx, h_params, N, S, pad)
+    if host is None:
+        idx, params = idx.to(data.device), params.to(data.device)
+    elif idx.device != data.device or params.device != data.device or tuple(idx.shape) != tuple(h_idx.shape) \
+            or tuple(params.shape) != tuple(h_params.shape) or idx.dtype != torch.int32 or params.dtype != torch.int32:
+        raise _lib.ConvNetHipError('crop_flip_normalize: the uploaded idx / params do not match their host copies')
+    idx, params = idx.contiguous(), params.contiguous()
+    lut = lut.to(device=data.device, dtype=torch.float32).contiguous()
+    V = idx.shape[0]
+    c_pad = _lib.chunk_elems(dtype)
+    out = torch.empty((V, 3, S, S) if form == 'nchw' else (V, S, S, c_pad), dtype=dtype, device=data.device)
+    PROFILER.run('augment_crop_flip', 1, 0.0, V * S * S * 3 + out.numel() * _esize(out),
+                 lambda: _L().cn_augment_crop_flip(ptr(data), data.numel(), ptr(idx), ptr(params), ptr(lut), ptr(out), N, V, S,
+                                                   pad, c_pad, code, 0 if form == 'nchw' else 1, stream_of(data)), data.device)
+    return out
+
+
 def nchw_to_pairs(x_nchw, pad):
     """fp32 NCHW (C <= 4) -> zero-padded bf16 pixel-pair image [N, H+2ph, (W+2pw)/2, 8] (cn_nchw_to_pairs)."""
     N, C, H, W = x_nchw.shape

@@ -338,9 +338,16 @@ class Trainer(object):
         for buf in self._model.buffers():
             self.reducer.broadcast_(buf, 0)
 
+    def _is_compute_nhwc(self, inputs):
+        """A batch already in the form the first convolution reads (data.DeviceCifarLoader): NHWC in the compute dtype, the
+        channels padded to one 16-byte chunk.  (In fp32 such a batch needs no special case: the cast below is the identity.)"""
+        return (inputs.dim() == 4 and inputs.dtype == self.dtype and self.dtype != torch.float32 and inputs.shape[1] != 3
+                and inputs.shape[-1] == _lib.chunk_elems(self.dtype) and inputs.device == self.device)
+
     def _to_device(self, inputs, target):
         target = target.to(self.device, non_blocking=True)
-        inputs = inputs.to(self.device, dtype=torch.float32, non_blocking=True)
+        if not self._is_compute_nhwc(inputs):
+            inputs = inputs.to(self.device, dtype=torch.float32, non_blocking=True)
         return inputs, target
 
     def _step(self, inputs_batch, target_batch, training=False, average_output=False, chunk_batch=1):
@@ -451,7 +458,7 @@ class Trainer(object):
     def _graph_ok(self, inputs, target):
         if not self._use_graph or self.device.type != 'cuda' or ops.PROFILER.enabled:
             return False
-        if not (inputs.is_cuda and target.is_cuda and inputs.dtype == torch.float32):
+        if not (inputs.is_cuda and target.is_cuda and (inputs.dtype == torch.float32 or self._is_compute_nhwc(inputs))):
             return False
         if not isinstance(self.criterion, CrossEntropyLoss) or not self._graph_model_ok:
             return False
@@ -645,9 +652,11 @@ class Trainer(object):
             info = rec.info()
             logging.debug('recorded the training step as a launch plan (%s): %d launches + %d imported on %d streams, '
                           '%d hand-offs, %d communicator calls', key[0], info[1], info[2], info[6], info[4], info[5])
-            # the input batch is read by this library's layout cast only (the model's first operator; _graph_ok admits
-            # fp32 device inputs, so torch converts nothing): its launches can be re-pointed at the caller's tensor.  The
-            # static copy is poisoned so that a reader the search missed shows up as NaN, not as a stale batch.
+            # the input batch is read by this library's kernels only: the layout cast of an fp32 NCHW batch, or - for a batch
+            # already in conv1's NHWC compute-dtype form (_is_compute_nhwc: data.DeviceCifarLoader) - conv1's forward and,
+            # later on the side stream, its weight gradient.  _graph_ok admits nothing else, so torch converts nothing, and
+            # every such launch can be re-pointed at the caller's tensor (_feed keeps that tensor alive until the next step).
+            # The static copy is poisoned so that a reader the search missed shows up as NaN, not as a stale batch.
             sites = L.cn_plan_bind_input(rec.handle, 0, ctypes.c_void_p(x.data_ptr()), x.numel() * x.element_size())
             if sites > 0:
                 x.fill_(float('nan'))

@@ -430,6 +430,18 @@ cn_status cn_resize_u8_crops(const unsigned char* pixels, const long long* meta,
 cn_status cn_resize_u8_views(const unsigned char* pixels, const long long* meta, const int* tables, const int* row_owner,
                              unsigned char* tmp, unsigned char* out, const long long* meta_host, long long pixel_bytes,
                              long long table_len, int V, int total_rows, int S, int C, void* stream);
+/* the CIFAR transform on a dataset resident in device memory (preprocess.py:44-54 random_crop, :185-227 Cutout): V views cut
+ * out of data[N][S][S][3] (uint8 HWC, data_bytes = N * S * S * 3).  View v reads image idx[v] with params[v][CN_AUGMENT_PARAMS] =
+ * {top, left, flip, y1, y2, x1, x2, 0}: (top, left) in [0, 2 * pad] is the window's corner in the image zero-padded by pad (a
+ * padded pixel is BYTE 0, lut[c][0] after Normalize), flip mirrors the window's columns, lut[3][256] is ToTensor + Normalize
+ * (as for cn_u8_nhwc_to_nchw_lut), and the rectangle [y1, y2) x [x1, x2) of the result is 0.0 (empty: no cutout).
+ * form 0: out = fp32 NCHW [V][3][S][S] (dtype CN_F32); form 1: out = NHWC [V][S][S][c_pad] in dtype, pad channels zero, c_pad =
+ * the dtype's 16-byte chunk - the same bits cn_nchw_to_nhwc makes of form 0.  A source position outside the image or the
+ * dataset reads as byte 0: no address outside data is formed whatever idx / params hold (the caller checks their ranges). */
+#define CN_AUGMENT_PARAMS 8
+cn_status cn_augment_crop_flip(const unsigned char* data, long long data_bytes, const int* idx, const int* params,
+                               const float* lut, void* out, int N, int V, int S, int pad, int c_pad, int dtype, int form,
+                               void* stream);
 /* Stride-2 stem (models/resnet.py:226, 7x7/2 pad 3 on 3 channels) in "pixel pair" form: the fp32 NCHW batch
  * becomes a zero-padded bf16 image [N][H+2*pad_h][(W+2*pad_w)/2][8] whose 16-byte chunks hold two adjacent
  * pixels x 4 channels; with the filter packed the same way (cn_weight_prep_pairs: [K][R][ceil(S/2)][8]) the
