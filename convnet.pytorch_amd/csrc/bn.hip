@@ -67,6 +67,41 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const char* y, float* par
 }
 
 
+// pivot[c] = mean of R rows of y spread evenly over the M rows (row i * rstride, i < R; all rows when M <= R): an
+// estimate of the batch mean good to a fraction of a standard deviation, which is all the centred sums of
+// bn_stats_kernel need of their pivot.  One workgroup per column group; R is a few hundred rows, so the launch is
+// latency only.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_pivot_kernel(const char* y, float* pivot, int C, int tpr_log2, int R,
+                                                      int rstride) {
+  constexpr int CH = ElemTraits<T>::kChunk;
+  constexpr int EB = ElemTraits<T>::kBytes;
+  __shared__ float red[256 * 2 * CH];
+  const int tid = threadIdx.x;
+  const int tpr = 1 << tpr_log2, rpp = 256 >> tpr_log2;
+  const int cpr = C / CH;
+  const int tcol = tid & (tpr - 1), rsub = tid >> tpr_log2;
+  const int col = blockIdx.x * tpr + tcol;
+  float s[CH], q[CH];
+#pragma unroll
+  for (int e = 0; e < CH; ++e) { s[e] = 0.f; q[e] = 0.f; }
+  if (col < cpr) {
+    const size_t cb = (size_t)col * CH * EB, rb = (size_t)C * EB;
+    for (int i = rsub; i < R; i += rpp) {
+      float f[CH];
+      Chunk<T>::unpack(cn_ld16(y + (size_t)i * rstride * rb + cb), f);
+#pragma unroll
+      for (int e = 0; e < CH; ++e) s[e] += f[e];
+    }
+  }
+  bn_block_colsum<CH>(s, q, red, tpr_log2, tid);
+  if (rsub == 0 && col < cpr) {
+    const float inv = 1.f / (float)R;
+#pragma unroll
+    for (int e = 0; e < CH; ++e) pivot[col * CH + e] = s[e] * inv;
+  }
+}
+
 // out[r2][col] = sum of the G consecutive partial rows r2*G .. r2*G+G-1 (fixed order).  Brings the
 // per-pixel-tile partials a convolution epilogue emitted (thousands of rows for the 56x56 layers) down
 // to the few hundred rows bn_finalize_kernel walks.
@@ -104,7 +139,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* partial, 
                                                          float* running_mean, float* running_var,
                                                          long long* num_batches_tracked, float momentum,
                                                          float eps, float* save_mean, float* save_invstd,
-                                                         float* scale, float* shift, int centered) {
+                                                         float* scale, float* shift, int centered,
+                                                         const float* pivot) {
   __shared__ double red[512];
   const int c = blockIdx.x * BN_FC + (threadIdx.x % BN_FC);
   const int part = threadIdx.x / BN_FC;
@@ -116,13 +152,14 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* partial, 
   const float b_pre = (owner && beta != nullptr) ? beta[c] : 0.f;
   const float rm_pre = (owner && running_mean != nullptr) ? running_mean[c] : 0.f;
   const float rv_pre = (owner && running_mean != nullptr) ? running_var[c] : 0.f;
+  const float pv_pre = (owner && pivot != nullptr) ? pivot[c] : rm_pre;
   double s, q;
   bn_sum_partials(partial, nrb, C, c, part, red, s, q);
   if (c >= C || part != 0) return;
-  // centred partials (sums of y - running_mean as it was before this update): the variance no longer comes out of
-  // the difference of two numbers of size mean^2
+  // centred partials (sums of y - pivot; the pivot is running_mean as it was before this update unless the caller
+  // supplies one): the variance no longer comes out of the difference of two numbers of size mean^2
   const double dmean = s / (double)M;
-  const double mean = centered ? (double)cn_pivot(rm_pre) + dmean : dmean;
+  const double mean = centered ? (double)cn_pivot(pv_pre) + dmean : dmean;
   double var = q / (double)M - dmean * dmean;
   if (var < 0.0) var = 0.0;
   const float invstd = (float)(1.0 / sqrt(var + (double)eps));
@@ -566,10 +603,10 @@ static int bn_fwd_tail(const float* partial, int nrb, const void* y, const void*
                        unsigned char* relu_mask, const float* gamma, const float* beta, float* running_mean,
                        float* running_var, long long* num_batches_tracked, float momentum, float eps,
                        float* stats_out, int M, int C, int relu, int dtype, const BnMap& m, hipStream_t stream,
-                       int centered) {
+                       int centered, const float* pivot = nullptr) {
   CN_LAUNCH(bn_finalize_kernel, dim3((unsigned)((C + BN_FC - 1) / BN_FC)), dim3(256), stream, partial, nrb,
             M, C, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, stats_out,
-            stats_out + C, stats_out + 2 * C, stats_out + 3 * C, centered);
+            stats_out + C, stats_out + 2 * C, stats_out + 3 * C, centered, pivot);
   if (z == nullptr) return cn_check_launch("bn_fwd_train");   // statistics only (the consumer applies them itself)
   int nab = bn_row_blocks(M, m, cn_get_option("bn_apply_blocks", BN_APPLY_BLOCKS));
   dim3 agrid((unsigned)nab, (unsigned)m.gy);
@@ -602,6 +639,35 @@ extern "C" cn_status cn_bn_fwd_train(const void* y, const void* residual, void* 
   CN_DISPATCH_T(dtype, CN_LAUNCH(bn_stats_kernel<TT>, grid, dim3(256), stream, (const char*)y, partial, M, C, m.tpr_log2, pivot));
   return bn_fwd_tail(partial, nrb, y, residual, z, relu_mask, gamma, beta, running_mean, running_var,
                      num_batches_tracked, momentum, eps, stats_out, M, C, relu, dtype, m, stream, pivot != nullptr);
+}
+
+// cn_bn_fwd_train with the statistics centred on an estimate of the batch mean itself (bn_pivot_kernel, written to
+// `pivot`, C floats of scratch) instead of the running mean: one more small launch, and the one-pass fp32 sums are as
+// exact at a cold start (running mean 0) or after a jump of the activations as they are in steady state.
+#define BN_PIVOT_ROWS 256
+extern "C" cn_status cn_bn_fwd_train_pivot(const void* y, const void* residual, void* z, unsigned char* relu_mask,
+                                           const float* gamma, const float* beta, float* running_mean,
+                                           float* running_var, long long* num_batches_tracked, float momentum,
+                                           float eps, float* stats_out, float* pivot, int M, int C, int relu, int dtype,
+                                           void* workspace, size_t ws_bytes, void* stream_) {
+  int rc = bn_check("bn_fwd_train_pivot", M, C, dtype);
+  if (rc) return rc;
+  if (pivot == nullptr) { cn_set_error("bn_fwd_train_pivot: no pivot scratch"); return CN_EINVAL; }
+  hipStream_t stream = (hipStream_t)stream_;
+  const int CH = cn_dtype_chunk(dtype);
+  BnMap m = bn_map(C / CH);
+  int nrb = bn_row_blocks(M, m, cn_get_option("bn_reduce_blocks", BN_REDUCE_BLOCKS));
+  if (workspace == nullptr || ws_bytes < (size_t)nrb * 2 * C * sizeof(float)) {
+    cn_set_error("bn_fwd_train_pivot: workspace too small");
+    return CN_EWORKSPACE;
+  }
+  float* partial = (float*)workspace;
+  const int R = M < BN_PIVOT_ROWS ? M : BN_PIVOT_ROWS;
+  CN_DISPATCH_T(dtype, CN_LAUNCH(bn_pivot_kernel<TT>, dim3((unsigned)m.gy), dim3(256), stream, (const char*)y, pivot, C, m.tpr_log2, R, M / R));
+  dim3 grid((unsigned)nrb, (unsigned)m.gy);
+  CN_DISPATCH_T(dtype, CN_LAUNCH(bn_stats_kernel<TT>, grid, dim3(256), stream, (const char*)y, partial, M, C, m.tpr_log2, (const float*)pivot));
+  return bn_fwd_tail(partial, nrb, y, residual, z, relu_mask, gamma, beta, running_mean, running_var,
+                     num_batches_tracked, momentum, eps, stats_out, M, C, relu, dtype, m, stream, 1, pivot);
 }
 
 // Training forward from statistics partials a producer already reduced (cn_conv2d_fwd_bnstats):

@@ -843,6 +843,11 @@ class DataRegime(object):
             if 'cifar' in setting['data']['name']:      # (the worker pipeline: fp32 batches from the host transforms)
                 for k in ('device_normalize', 'device_resize'):
                     setting['transform'].pop(k, None)
+            if setting['data'].get('transform') is not None:
+                # an explicit `transform` (mobilenet's default data_regime) is a host pipeline that ends in fp32 CHW
+                # tensors: nothing is left for the device-side passes, the loader yields fp32 NCHW as with --host-normalize
+                for k in ('device_normalize', 'device_resize'):
+                    setting['transform'].pop(k, None)
             self._transform = get_transform(**setting['transform'])
             setting['data'].setdefault('transform', self._transform)
             self._data = get_dataset(**setting['data'])

@@ -129,6 +129,10 @@ class ParamArena(object):
             krsc_off = off
             off += _round_up(n, _ALIGN)
             want_crsk = not grouped and (isinstance(mod, cnn.Linear) or (getattr(mod, 'needs_dgrad', True) and cpad == creal))
+            if getattr(mod, 'depthwise', False):
+                # depthwise filter [C][3][3][1]: its CRSK copy IS the tap-major [3][3][C] filter the dwconv kernels read
+                # (forward, data gradient), written by the same tiled launch
+                want_crsk = True
             crsk_off = -1
             if want_crsk:
                 crsk_off = off

@@ -59,21 +59,26 @@ class _ArenaModule(tnn.Module):
 class Conv2d(_ArenaModule):
     """nn.Conv2d(in, out, kernel_size, stride, padding, dilation, groups, bias) - dilation=1; groups > 1 only as the
     grouped 3x3 convolution of a ResNeXt block (3x3, stride 1 or 2, padding 1, no bias, 1 <= C/g, K/g <= 64:
-    ops.GroupedConv2dFunction on csrc/gconv.hip)."""
+    ops.GroupedConv2dFunction on csrc/gconv.hip) or, with groups == in == out channels, as the depthwise 3x3 convolution of
+    a MobileNet block (stride 1 or 2, padding 1, with or without bias: ops.DepthwiseConv2dFunction on csrc/dwconv.hip)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
                  bias=True, padding_mode='zeros'):
         super().__init__()
         if _pair(dilation) != (1, 1) or padding_mode != 'zeros':
             raise NotImplementedError('HIP Conv2d supports dilation=1, zero padding')
+        # depthwise: one filter per channel (MobileNet), with or without bias: ops.DepthwiseConv2dFunction on csrc/dwconv.hip
+        self.depthwise = (groups > 1 and groups == in_channels == out_channels and _pair(kernel_size) == (3, 3)
+                          and _pair(stride) in ((1, 1), (2, 2)) and _pair(padding) == (1, 1))
         if groups != 1:
             ok = (groups > 1 and in_channels % groups == 0 and out_channels % groups == 0
                   and 1 <= in_channels // groups <= 64 and 1 <= out_channels // groups <= 64
                   and _pair(kernel_size) == (3, 3) and _pair(stride) in ((1, 1), (2, 2)) and _pair(padding) == (1, 1)
-                  and not bias)
+                  and (not bias or self.depthwise))
             if not ok:
                 raise NotImplementedError(
                     'HIP Conv2d supports groups > 1 only as a 3x3 / stride 1 or 2 / padding 1 convolution without bias '
+                    '(depthwise, groups == in == out: with or without) '
                     'whose groups divide in and out channels with 1 <= channels per group <= 64 (got in=%d out=%d '
                     'kernel=%s stride=%s padding=%s groups=%d bias=%s)'
                     % (in_channels, out_channels, kernel_size, stride, padding, groups, bias))
@@ -112,6 +117,14 @@ class Conv2d(_ArenaModule):
             if x.shape[-1] != self.in_channels:
                 raise _lib.ConvNetHipError('grouped Conv2d expected %d NHWC channels, got %s'
                                            % (self.in_channels, tuple(x.shape)))
+            if self.depthwise and ops.DWCONV:
+                if not ops.dwconv_ok(self.in_channels, self.kernel_size, self.stride, self.padding, x.dtype):
+                    raise NotImplementedError('depthwise Conv2d of %d channels in %s: channels must be a multiple of '
+                                              'the dtype\'s chunk' % (self.in_channels, x.dtype))
+                return ops.DepthwiseConv2dFunction.apply(x, self.weight, self.bias, self)
+            if self.bias is not None:
+                raise NotImplementedError('depthwise Conv2d with a bias needs the depthwise kernels (flag dwconv=0 '
+                                          'routes the layer to the grouped kernels, which carry no bias)')
             if not ops.gconv2d_ok(self.in_channels, self.out_channels, self.groups, self.kernel_size, self.stride,
                                   self.padding, x.dtype):
                 raise NotImplementedError('grouped Conv2d %d -> %d (groups %d) in %s: channels must be multiples of the '
@@ -211,6 +224,10 @@ class BatchNorm2d(_ArenaModule):
         self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
         self._host_batches = 0  # host mirror of num_batches_tracked (momentum=None averaging)
         self.sync_group = None  # set by convert_sync_batchnorm: batch statistics over all ranks
+        # True: in fp32 the standalone statistics pass centres its one-pass sums on an estimate of the batch mean
+        # (cn_bn_fwd_train_pivot) instead of the running mean - exact from a cold start, one more small launch.  Set
+        # by a model (models/mobilenet.py); the default keeps every other model's numbers as they are
+        self.batch_pivot = False
 
     def reset_running_stats(self):
         self.running_mean.zero_()

@@ -768,6 +768,59 @@ def gconv2d_wgrad(x, dy, dw, K, groups, stride, beta=1.0, scale=1.0, tag='main')
                  x.device, detail=_conv_detail('gwgrad', C, H, K, 3, (stride, stride)))
 
 
+# depthwise 3x3 convolutions (csrc/dwconv.hip): filter w_rsc [3][3][C] in the compute dtype (the tap-major copy), bias [C]
+# fp32 or None, stride 1 or 2, padding 1.  2 * 9 FLOPs per output element, bytes the algorithmic traffic.
+DWCONV = flags.on('dwconv')
+
+
+def dwconv_ok(C, kernel_size, stride, padding, dtype):
+    return bool(_L().cn_dwconv3x3_ok(C, kernel_size[0], kernel_size[1], stride[0], stride[1], padding[0], padding[1],
+                                     dtype_code(dtype)))
+
+
+def dwconv_fwd(x, w_rsc, bias, stride):
+    N, H, W, C = x.shape
+    P, Q = conv_out_hw(H, W, 3, 3, (stride, stride), (1, 1))
+    y = torch.empty((N, P, Q, C), dtype=x.dtype, device=x.device)
+    PROFILER.run(_last_kernel(), 1, 2.0 * y.numel() * 9,
+                 x.numel() * _esize(x) + y.numel() * _esize(y) + C * 9 * _esize(x),
+                 lambda: _L().cn_dwconv3x3_fwd(ptr(x), ptr(w_rsc), ptr(bias), ptr(y), N, H, W, C, stride,
+                                               dtype_code(x.dtype), stream_of(x)),
+                 x.device, detail=_conv_detail('dwfwd', C, H, C, 3, (stride, stride)))
+    return y
+
+
+def dwconv_dgrad(dy, w_rsc, x_shape, stride):
+    N, H, W, C = x_shape
+    dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+    PROFILER.run(_last_kernel(), 1, 2.0 * dy.numel() * 9,
+                 dy.numel() * _esize(dy) + dx.numel() * _esize(dx) + C * 9 * _esize(dy),
+                 lambda: _L().cn_dwconv3x3_dgrad(ptr(dy), ptr(w_rsc), ptr(dx), N, H, W, C, stride,
+                                                 dtype_code(dy.dtype), stream_of(dy)),
+                 dy.device, detail=_conv_detail('dwdgrad', C, H, C, 3, (stride, stride)))
+    return dx
+
+
+def dwconv_wgrad_split(x_shape, stride, dtype):
+    """Number of pixel slabs (workspace partials) the weight gradient of this shape is split into."""
+    N, H, W, C = x_shape
+    return _L().cn_dwconv3x3_wgrad_workspace(N, H, W, C, stride, dtype_code(dtype)) // (C * 10 * 4)
+
+
+def dwconv_wgrad(x, dy, dw, dbias, stride, beta=1.0, scale=1.0, tag='main'):
+    """dw (fp32, [C][3][3] memory order: the parameter's own) = beta*dw + scale*wgrad; dbias (fp32 [C] or None) likewise."""
+    N, H, W, C = x.shape
+    code = dtype_code(x.dtype)
+    L = _L()
+    need = L.cn_dwconv3x3_wgrad_workspace(N, H, W, C, stride, code)
+    ws = workspace(need, x.device, tag)
+    PROFILER.run(_last_kernel(' (+wgrad_reduce)'), 3 if dbias is not None else 2, 2.0 * dy.numel() * 10,
+                 x.numel() * _esize(x) + dy.numel() * _esize(dy) + 2.0 * need + C * 10 * 4,
+                 lambda: L.cn_dwconv3x3_wgrad(ptr(x), ptr(dy), ptr(dw), ptr(dbias), N, H, W, C, stride, code, beta, scale,
+                                              ptr(ws), ws.numel() * 4, stream_of(x)),
+                 x.device, detail=_conv_detail('dwwgrad', C, H, C, 3, (stride, stride)))
+
+
 def weight_prep(w_master_krsc, w_krsc, w_crsk, Co, taps, c_real, c_pad):
     PROFILER.run('weight_prep', 1, 0.0, Co * taps * c_real * 4 + Co * taps * c_pad * _esize(w_krsc) * (2 if w_crsk is not None else 1),
                  lambda: _L().cn_weight_prep(ptr(w_master_krsc), ptr(w_krsc), ptr(w_crsk), Co, taps, c_real,
@@ -1191,6 +1244,44 @@ class GroupedConv2dFunction(Function):
         return dx, None, None
 
 
+class DepthwiseConv2dFunction(Function):
+    """A depthwise 3x3 convolution (MobileNet's per-channel filter, with or without bias) on csrc/dwconv.hip.  Like the
+    grouped convolution it takes part in no fusion.  The weight AND bias gradients come from one pass (dwconv_wgrad) on the
+    side stream; the data gradient is launched first (dgrad_first) and skipped when the input needs none."""
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod):
+        mod.ensure_prepared()
+        _refuse_parked(mod, 'depthwise convolution')
+        y = dwconv_fwd(x, mod.w_crsk, bias, mod.stride[0])
+        ctx.mod = mod
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x)
+        COUNTERS['dwconv'] = COUNTERS.get('dwconv', 0) + 1
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        mod = ctx.mod
+        _refuse_parked(mod, 'depthwise convolution')
+        if _is_zero_placeholder(dy):
+            raise _lib.ConvNetHipError('depthwise convolution: a lazy gradient reached it (depthwise convs take no fusion)')
+        dy = dy.contiguous()
+        st = mod.stride[0]
+        db = mod.grad_view('bias') if ctx.has_bias else None
+
+        def submit_wgrad():
+            _submit_wgrad(mod, lambda tag: dwconv_wgrad(x, dy, mod.grad_view('weight'), db, st, tag=tag), (x, dy), dy)
+
+        if not DGRAD_FIRST:
+            submit_wgrad()
+        need_dx = ctx.needs_input_grad[0] and getattr(mod, 'needs_dgrad', True)
+        dx = dwconv_dgrad(dy, mod.w_crsk, x.shape, st) if need_dx else None
+        if DGRAD_FIRST:
+            submit_wgrad()
+        return dx, None, None, None
+
+
 def _sync_group(mod):
     """(process group, world size) when this BatchNorm synchronises its batch statistics across ranks
     (nn.convert_sync_batchnorm + an initialised process group of more than one rank), else None."""
@@ -1369,6 +1460,19 @@ class BatchNormActFunction(Function):
                              ptr(y), ptr(residual) if zk is not None else None, ptr(zk), ptr(mask) if zk is not None else None,
                              ptr(gamma), ptr(beta), *_running_ptrs(mod), momentum, mod.eps, ptr(stats), M, C, int(relu), code,
                              ptr(ps.partial), ps.rows, ptr(ws), ws.numel() * 4, stream_of(y)),
+                         y.device)
+        elif getattr(mod, 'batch_pivot', False) and y.dtype == torch.float32:
+            # statistics centred on an estimate of the batch mean (nn.BatchNorm2d.batch_pivot).  fp32 storage only: behind
+            # the 2^-9 rounding of a 16-bit y the 1e-5 this buys cannot be seen, and the extra launch can
+            pivot = torch.empty(C, dtype=torch.float32, device=y.device)
+            PROFILER.run('bn_pivot+bn_stats+bn_finalize+bn_apply' if zk is not None else 'bn_pivot+bn_stats+bn_finalize',
+                         4 if zk is not None else 3, 0.0,
+                         nb * (4 if residual is not None else 3) + (mask.numel() if mask is not None else 0)
+                         if zk is not None else nb,
+                         lambda: L.cn_bn_fwd_train_pivot(
+                             ptr(y), ptr(residual) if zk is not None else None, ptr(zk), ptr(mask) if zk is not None else None,
+                             ptr(gamma), ptr(beta), *_running_ptrs(mod), momentum, mod.eps, ptr(stats), ptr(pivot), M, C,
+                             int(relu), code, ptr(ws), ws.numel() * 4, stream_of(y)),
                          y.device)
         else:
             PROFILER.run('bn_stats+bn_finalize+bn_apply' if zk is not None else 'bn_stats+bn_finalize', 3 if zk is not None else 2, 0.0,

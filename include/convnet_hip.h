@@ -225,6 +225,26 @@ cn_status cn_gconv2d_dgrad(const void* dy, const void* w, void* dx, int N, int H
 size_t cn_gconv2d_wgrad_workspace(int N, int H, int W, int C, int K, int groups, int stride, int dtype);
 cn_status cn_gconv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int C, int K, int groups, int stride,
                            int dtype, float beta, float scale, void* workspace, size_t ws_bytes, void* stream);
+/* Depthwise 3x3 convolution, stride 1 or 2, padding 1 (the first convolution of a MobileNet block, the reference's
+ * models/mobilenet.py: nn.Conv2d(C, C, 3, stride, 1, groups=C), bias included) on the VALU (csrc/dwconv.hip): a lane owns a
+ * 16-byte channel chunk and a run of output pixels.  NHWC activations in the compute dtype, fp32 accumulation; the filter
+ * w_rsc is the TAP-MAJOR compute-dtype copy [3][3][C] (the parameter [C][1][3][3] transposed; cn_weight_prep's CRSK copy of
+ * a one-input-channel filter), bias [C] fp32 or NULL.
+ *   fwd:   y[N][P][Q][C] = conv(x[N][H][W][C], w) + bias, P = (H - 1) / stride + 1
+ *   dgrad: dx[N][H][W][C] from dy[N][P][Q][C] and the same filter copy (gather form, no atomics)
+ *   wgrad: dw[C][3][3] (fp32, the parameter's own order) = beta*dw + scale*wgrad(x, dy) and, when dbias is not NULL,
+ *          dbias[C] = beta*dbias + scale*sum_pixels dy; beta = 0 does not read the old contents.  Split reduction through
+ *          `workspace` (cn_dwconv3x3_wgrad_workspace bytes = slabs * C * 10 floats), fixed summation order.
+ * cn_dwconv3x3_ok: C a multiple of the dtype's chunk, 3x3, equal strides of 1 or 2, padding 1; every other configuration is
+ * refused with CN_ESHAPE. */
+int cn_dwconv3x3_ok(int C, int R, int S, int stride_h, int stride_w, int pad_h, int pad_w, int dtype);
+cn_status cn_dwconv3x3_fwd(const void* x, const void* w_rsc, const float* bias, void* y, int N, int H, int W, int C, int stride,
+                           int dtype, void* stream);
+cn_status cn_dwconv3x3_dgrad(const void* dy, const void* w_rsc, void* dx, int N, int H, int W, int C, int stride, int dtype,
+                             void* stream);
+size_t cn_dwconv3x3_wgrad_workspace(int N, int H, int W, int C, int stride, int dtype);
+cn_status cn_dwconv3x3_wgrad(const void* x, const void* dy, float* dw, float* dbias, int N, int H, int W, int C, int stride,
+                             int dtype, float beta, float scale, void* workspace, size_t ws_bytes, void* stream);
 /* dw[K,R,S,C_real] (fp32) = beta*dw + scale * sum_pixels dy (x) x ; split reduction through
  * `workspace` (cn_conv2d_wgrad_workspace bytes), fixed summation order. */
 size_t cn_conv2d_wgrad_workspace(int N, int H, int W, int C, int K, int R, int S, int stride_h, int stride_w,
@@ -273,6 +293,13 @@ cn_status cn_bn_fwd_train(const void* y, const void* residual, void* z, unsigned
                           float* running_mean, float* running_var, long long* num_batches_tracked, float momentum,
                           float eps, float* stats_out, int M, int C, int relu, int dtype, void* workspace,
                           size_t ws_bytes, void* stream);
+/* cn_bn_fwd_train with the one-pass statistics centred on an estimate of the batch mean (the mean of up to 256 rows spread
+ * over y, one more small launch) instead of the running mean, which is 0 at a cold start: the variance of a layer whose
+ * mean is not small against its deviation keeps fp32 accuracy from the first step on.  pivot: C floats of scratch. */
+cn_status cn_bn_fwd_train_pivot(const void* y, const void* residual, void* z, unsigned char* relu_mask, const float* gamma,
+                                const float* beta, float* running_mean, float* running_var, long long* num_batches_tracked,
+                                float momentum, float eps, float* stats_out, float* pivot, int M, int C, int relu, int dtype,
+                                void* workspace, size_t ws_bytes, void* stream);
 /* cn_bn_fwd_train with the statistics partials supplied by the producer of y (cn_conv2d_fwd_bnstats):
  * partial = [nrb][2*C] floats. */
 cn_status cn_bn_fwd_train_partials(const void* y, const void* residual, void* z, unsigned char* relu_mask,
