@@ -691,6 +691,243 @@ __global__ __launch_bounds__(512) void jbwd_kernel(JbParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Junction pair that RECOMPUTES the BatchNorm input: at every site of the model y is the output of the very
+// convolution whose gradients are formed here (y = conv1x1(x, w), no bias), and the kernel holds x and w anyway.  So
+// y is not read (CO of the 2*CO + CI elements per pixel): per stage the waves form the y tile from the x tile in LDS
+// and the filter's KRSC copy in registers by jfwd_kernel's recipe (A = w[co][ci] rows, B = x pixel rows, kk ascending,
+// fp32 accumulators from zero, cn_pack2<T>) - the same instructions in the same roles and order, so the same bits as
+// the stored y - and write it, rounded, into the dyT buffer (8-byte stores of 4 consecutive channels, same pitch and
+// swizzle).  After a barrier each thread turns the 16-byte chunks it owns into dy in place with jbwd_kernel's
+// fmaf(c1, g, fmaf(c2, y, c3)); a second barrier, then both products as in jbwd_kernel.  No LDS beyond jbwd_kernel's.
+// The registers that held y hold a second g buffer: the loads of stage s + 1 are issued at the start of stage s and
+// stay in flight across all four phases.  The x tile carries dyT's chunk swizzle here (the y product reads whole
+// pixel rows of it with ds_read_b128: 16 rows on 16 bank groups); the transpose reads are unaffected (see above).
+struct JbRyParams {
+  const char* g;      // [M][CO] masked upstream gradient of the BatchNorm
+  const float* coef;  // [3][CO]
+  const char* w;      // [CI][CO] filter in data-gradient (CRSK) order
+  const char* wk;     // [CO][CI] filter in forward (KRSC) order: the y product's A operand
+  const char* x;      // [M][CI] convolution input
+  char* dx;           // [M][CI]
+  float* part;        // [nsplit][CO][CI]
+  int M, m_per_split, nsplit;
+  unsigned int g_bytes, x_bytes;
+};
+
+template <typename T, int CO, int CI, int BM>
+__global__ __launch_bounds__(512) void jbwd_kernel_ry(JbRyParams p) {
+  static_assert(sizeof(T) == 2, "16-bit storage");
+  static_assert(CO % 32 == 0 && CI % 32 == 0 && BM % 64 == 0, "tile shapes");
+  constexpr int PD = CO * 2 + 64;   // dy tile pitch (bytes)
+  constexpr int PX = CI * 2 + 64;   // x tile pitch
+  constexpr int PW = CO * 2;        // filter rows (ci), chunk-swizzled
+  constexpr int NCG = CO / 8;       // 16-byte chunks per g row
+  constexpr int NCX = CI / 8;
+  constexpr int RG = 512 / NCG, RX = 512 / NCX;   // rows per load pass
+  constexpr int NG = BM / RG, NX = BM / RX;
+  static_assert(NG >= 1 && NX >= 1 && BM % RG == 0 && BM % RX == 0, "load passes");
+  constexpr int NPT = BM / 32, NCT = CI / 32, NOT = CO / 32;   // 32 x 32 output tiles: dx is NPT x NCT, dW is NOT x NCT
+  constexpr int NKY = CI / 16;                                  // k-steps of the y product
+  static_assert(NPT * NCT == 8, "one data-gradient tile per wave");
+  static_assert(NOT == 8, "one weight-gradient row of tiles (and one 32-channel column of y) per wave");
+  static_assert(NCX % 4 == 0, "x rows are whole 64-byte swizzle granules");
+  __shared__ __attribute__((aligned(16))) char lds[BM * PD + BM * PX + CI * PW + 3 * CO * 4];
+  char* dyT = lds;
+  char* xT = lds + BM * PD;
+  char* wT = lds + BM * PD + BM * PX;
+  float* s_coef = (float*)(lds + BM * PD + BM * PX + CI * PW);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = cn_uniform(tid >> 6);
+  const int split = blockIdx.x;
+  const int m_begin = split * p.m_per_split;
+  int m_end = m_begin + p.m_per_split;
+  if (m_end > p.M) m_end = p.M;
+  const int L = lane & 15, g1 = (lane >> 4) & 1, h = lane >> 5;
+
+  // filter copies (whole launch): CRSK in LDS for the data gradient, this wave's 32 KRSC rows in registers for y
+  for (int id = tid; id < CI * NCG; id += 512) {
+    const int row = id / NCG, c = id - row * NCG;
+    cn_st16(wT + row * PW + ((c ^ (row & (NCG - 1))) << 4), cn_ld16(p.w + ((size_t)row * CO + (size_t)c * 8) * 2));
+  }
+  for (int c = tid; c < 3 * CO; c += 512) s_coef[c] = p.coef[c];
+  s16x8 wf[NKY];
+#pragma unroll
+  for (int kk = 0; kk < NKY; ++kk)
+    wf[kk] = __builtin_bit_cast(s16x8, cn_ld16(p.wk + ((size_t)(wave * 32 + (lane & 31)) * CI + 16 * kk + 8 * h) * 2));
+  __syncthreads();
+
+  const cn_buf_t gbuf = cn_make_buf(p.g, p.g_bytes);
+  const cn_buf_t xbuf = cn_make_buf(p.x, p.x_bytes);
+  const int colG = tid % NCG, rowG0 = tid / NCG;
+  const int colX = tid % NCX, rowX0 = tid / NCX;
+  auto swz = [](int chunk, int row) { return (chunk & ~3) | ((chunk & 3) ^ ((row >> 2) & 3)); };
+
+  u32x4 regGa[NG], regGb[NG], regX[NX];
+  unsigned int okGa = 0, okGb = 0;
+  auto load_g = [&](int mb, u32x4 (&rg)[NG], unsigned int& okG) {
+    okG = 0;
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+      const int m = mb + rowG0 + i * RG;
+      const bool ok = m < m_end;
+      okG |= (ok ? 1u : 0u) << i;
+      rg[i] = cn_buf_ld16(gbuf, ok ? ((unsigned int)m * (unsigned int)CO + (unsigned int)colG * 8u) * 2u : CN_OOB);
+    }
+  };
+  auto load_x = [&](int mb) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      const int m = mb + rowX0 + i * RX;
+      regX[i] = cn_buf_ld16(xbuf, m < m_end ? ((unsigned int)m * (unsigned int)CI + (unsigned int)colX * 8u) * 2u : CN_OOB);
+    }
+  };
+
+  f32x16 accw[NCT];
+#pragma unroll
+  for (int b = 0; b < NCT; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accw[b][r] = 0.f;
+  const int pt = wave / NCT, ct = wave % NCT;   // this wave's data-gradient tile: pixels pt*32.., input channels ct*32..
+
+  auto mma = [&](const s16x8& a, const s16x8& b, f32x16& c) {
+    if constexpr (std::is_same<T, f16_t>::value) c = cn_mfma_32x32x16_f16(a, b, c);
+    else c = cn_mfma_32x32x16_bf16(a, b, c);
+  };
+  // ---- y[pixel][co] of this wave's 32 output channels, all BM pixels: jfwd_kernel's product, rounded, into dyT
+  auto form_y = [&]() {
+#pragma unroll 1
+    for (int t = 0; t < NPT; ++t) {   // (one tile's accumulators at a time: the two g buffers leave no room for four)
+      const int prow = t * 32 + (lane & 31);
+      const char* rowp = xT + prow * PX;
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+      for (int kk = 0; kk < NKY; ++kk)
+        mma(wf[kk], __builtin_bit_cast(s16x8, cn_ld16(rowp + (swz(2 * kk + h, prow) << 4))), acc);
+      char* dst = dyT + prow * PD + 8 * h;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {   // channels wave*32 + 8*q + 4*h .. + 3: half of chunk wave*4 + q
+        u32x2 pk;
+        pk[0] = cn_pack2<T>(acc[q * 4], acc[q * 4 + 1]);
+        pk[1] = cn_pack2<T>(acc[q * 4 + 2], acc[q * 4 + 3]);
+        *(u32x2*)(dst + (swz(wave * 4 + q, prow) << 4)) = pk;
+      }
+    }
+  };
+  // ---- dy = c1*g + c2*y + c3 in place: bn_bwd_apply_kernel's operation order and rounding, as jbwd_kernel
+  auto form_dy = [&](const u32x4 (&rg)[NG], unsigned int okG) {
+    float c1[8], c2[8], c3[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      c1[e] = s_coef[colG * 8 + e];
+      c2[e] = s_coef[CO + colG * 8 + e];
+      c3[e] = s_coef[2 * CO + colG * 8 + e];
+    }
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+      const int row = rowG0 + i * RG;
+      char* slot = dyT + row * PD + (swz(colG, row) << 4);
+      float gg[8], vv[8];
+      Chunk<T>::unpack(rg[i], gg);
+      Chunk<T>::unpack(cn_ld16(slot), vv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gg[e] = fmaf(c1[e], gg[e], fmaf(c2[e], vv[e], c3[e]));
+      cn_st16(slot, ((okG >> i) & 1u) ? Chunk<T>::pack(gg) : cn_zero16());   // rows past the range stay zero
+    }
+  };
+  auto compute = [&](int mb) {
+    // ---- data gradient: D[i = ci][j = pixel], k = co ascending in steps of 16 (igemm_kernel's order)
+    f32x16 accd;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accd[r] = 0.f;
+    {
+      const int wrow = ct * 32 + (lane & 31);
+      const int prow = pt * 32 + (lane & 31);
+      const char* wbase = wT + wrow * PW;
+      const char* dbase = dyT + prow * PD;
+      const int wsw = wrow & (NCG - 1);
+#pragma unroll 4
+      for (int kk = 0; kk < CO / 16; ++kk) {
+        const int c = 2 * kk + h;
+        const s16x8 a = __builtin_bit_cast(s16x8, cn_ld16(wbase + ((c ^ wsw) << 4)));
+        const s16x8 b = __builtin_bit_cast(s16x8, cn_ld16(dbase + (swz(c, prow) << 4)));
+        mma(a, b, accd);
+      }
+      const int m = mb + prow;
+      if (m < m_end) {
+        char* dst = p.dx + ((size_t)m * CI + (size_t)(ct * 32 + 4 * h)) * 2;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {   // 4 consecutive input channels per lane and q
+          u32x2 pk;
+          pk[0] = cn_pack2<T>(accd[q * 4], accd[q * 4 + 1]);
+          pk[1] = cn_pack2<T>(accd[q * 4 + 2], accd[q * 4 + 3]);
+          *(u32x2*)(dst + q * 16) = pk;
+        }
+      }
+    }
+    // ---- weight gradient: D[i = co][j = ci], k = the BM pixels of this stage
+#pragma unroll
+    for (int kk = 0; kk < BM / 16; ++kk) {
+      const int rbase = kk * 16 + h * 8 + (L >> 2);   // (rbase + 4) >> 2 = (rbase >> 2) + 1
+      const int cbase = g1 * 16 + (L & 3) * 4;
+      const int col = wave * 32 + cbase;              // this wave's 32 output channels
+      const s16x4 lo = cn_lds_read_tr16_b64(dyT + rbase * PD + (swz(col >> 3, rbase) << 4) + (col & 7) * 2);
+      const s16x4 hi = cn_lds_read_tr16_b64(dyT + (rbase + 4) * PD + (swz(col >> 3, rbase + 4) << 4) + (col & 7) * 2);
+      const s16x8 af = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+      for (int b = 0; b < NCT; ++b) {
+        const int cx = b * 32 + cbase;
+        const s16x4 xl = cn_lds_read_tr16_b64(xT + rbase * PX + (swz(cx >> 3, rbase) << 4) + (cx & 7) * 2);
+        const s16x4 xh = cn_lds_read_tr16_b64(xT + (rbase + 4) * PX + (swz(cx >> 3, rbase + 4) << 4) + (cx & 7) * 2);
+        const s16x8 bf = __builtin_shufflevector(xl, xh, 0, 1, 2, 3, 4, 5, 6, 7);
+        mma(af, bf, accw[b]);
+      }
+    }
+  };
+  // one stage: x tile -> y tile -> dy tile -> both products; the next stage's g lands in the other register buffer
+  auto stage = [&](int mb, const u32x4 (&cur)[NG], unsigned int okc, u32x4 (&nxt)[NG], unsigned int& okn) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      const int row = rowX0 + i * RX;
+      cn_st16(xT + row * PX + (swz(colX, row) << 4), regX[i]);
+    }
+    __syncthreads();
+    if (mb + BM < m_end) {
+      load_x(mb + BM);
+      load_g(mb + BM, nxt, okn);
+    }
+    form_y();
+    __syncthreads();
+    form_dy(cur, okc);
+    __syncthreads();
+    compute(mb);
+    __syncthreads();
+  };
+
+  if (m_begin < m_end) {
+    load_x(m_begin);
+    load_g(m_begin, regGa, okGa);
+    for (int mb = m_begin; mb < m_end; mb += 2 * BM) {
+      stage(mb, regGa, okGa, regGb, okGb);
+      if (mb + BM < m_end) stage(mb + BM, regGb, okGb, regGa, okGa);
+    }
+  }
+  float* out = p.part + (size_t)split * (size_t)CO * (size_t)CI;
+#pragma unroll
+  for (int b = 0; b < NCT; ++b) {
+    const int col = b * 32 + (lane & 31);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int co = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      out[(size_t)co * CI + col] = accw[b][r];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // 3x3 / stride 1 / pad 1 weight gradient with the activation staged ONCE per band of image rows (round 3).
 //
 // The tile kernels above treat every tap as its own block of GEMM columns: each (co, tap*ci) tile re-gathers its
@@ -1185,12 +1422,13 @@ extern "C" size_t cn_conv2d_bwd1x1_lazy_workspace(int N, int H, int W, int C, in
 // K output channels) for the upstream gradient dy = c1*g + c2*bn_y + c3 (coef = [c1 | c2 | c3], 3*K floats), formed
 // on load: cn_conv2d_dgrad_lazy + cn_conv2d_wgrad_lazy in one pass over g and bn_y.  dx has the bits of
 // cn_conv2d_dgrad_lazy; dw differs from cn_conv2d_wgrad_lazy by fp32 summation order only (other pixel ranges).
-extern "C" cn_status cn_conv2d_bwd1x1_lazy(const void* x, const void* g, const void* bn_y, const float* coef,
-                                           const void* w_crsk, void* dx, float* dw_krsc, int N, int H, int W, int C, int K,
-                                           int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
-                                           void* stream) {
-  if (x == nullptr || g == nullptr || bn_y == nullptr || coef == nullptr || w_crsk == nullptr || dx == nullptr ||
-      dw_krsc == nullptr) { cn_set_error("conv2d_bwd1x1_lazy: null operand"); return CN_EINVAL; }
+// bn_y given: it is read (jbwd_kernel).  bn_y == nullptr: it is conv1x1(x, w) and is recomputed from x and the
+// filter's KRSC copy w_krsc (jbwd_kernel_ry).
+static cn_status jb_run(const void* x, const void* g, const void* bn_y, const float* coef, const void* w_crsk,
+                        const void* w_krsc, void* dx, float* dw_krsc, int N, int H, int W, int C, int K, int dtype,
+                        float beta, float scale, void* workspace, size_t ws_bytes, void* stream) {
+  if (x == nullptr || g == nullptr || (bn_y == nullptr && w_krsc == nullptr) || coef == nullptr || w_crsk == nullptr ||
+      dx == nullptr || dw_krsc == nullptr) { cn_set_error("conv2d_bwd1x1_lazy: null operand"); return CN_EINVAL; }
   if (!cn_conv2d_bwd1x1_lazy_ok(C, K, dtype)) { cn_set_error("conv2d_bwd1x1_lazy: C=%d K=%d dtype %d is not an instantiated shape", C, K, dtype); return CN_ESHAPE; }
   const long long M = (long long)N * H * W;
   if (M <= 0) { cn_set_error("conv2d_bwd1x1_lazy: empty"); return CN_ESHAPE; }
@@ -1201,21 +1439,49 @@ extern "C" cn_status cn_conv2d_bwd1x1_lazy(const void* x, const void* g, const v
   mps = (mps + 127) / 128 * 128;
   const int nsplit = (int)((M + mps - 1) / mps);
   if (workspace == nullptr || ws_bytes < (size_t)nsplit * K * C * sizeof(float)) { cn_set_error("conv2d_bwd1x1_lazy: workspace too small"); return CN_EWORKSPACE; }
-  JbParams p;
-  memset(&p, 0, sizeof(p));
-  p.g = (const char*)g; p.y = (const char*)bn_y; p.coef = coef; p.w = (const char*)w_crsk; p.x = (const char*)x;
-  p.dx = (char*)dx; p.part = (float*)workspace;
-  p.M = (int)M; p.m_per_split = (int)mps; p.nsplit = nsplit;
-  p.gy_bytes = (unsigned int)gyb; p.x_bytes = (unsigned int)xb;
   hipStream_t st = (hipStream_t)stream;
   const int phase = cn_get_option("wgrad_phase", 0);   // measurement only, as cn_conv2d_wgrad
-  if (phase != 2) {
+  if (phase != 2 && bn_y != nullptr) {
+    JbParams p;
+    memset(&p, 0, sizeof(p));
+    p.g = (const char*)g; p.y = (const char*)bn_y; p.coef = coef; p.w = (const char*)w_crsk; p.x = (const char*)x;
+    p.dx = (char*)dx; p.part = (float*)workspace;
+    p.M = (int)M; p.m_per_split = (int)mps; p.nsplit = nsplit;
+    p.gy_bytes = (unsigned int)gyb; p.x_bytes = (unsigned int)xb;
     cn_set_last_kernel("jbwd_kernel<%s, 256, 64, 128>", dtype == CN_F16 ? "f16_t" : "bf16_t");
     if (dtype == CN_F16) CN_LAUNCH((jbwd_kernel<f16_t, 256, 64, 128>), dim3((unsigned)nsplit), dim3(512), st, p);
     else CN_LAUNCH((jbwd_kernel<bf16_t, 256, 64, 128>), dim3((unsigned)nsplit), dim3(512), st, p);
     int rc = cn_check_launch("jbwd");
     if (rc) return rc;
+  } else if (phase != 2) {
+    JbRyParams p;
+    memset(&p, 0, sizeof(p));
+    p.g = (const char*)g; p.coef = coef; p.w = (const char*)w_crsk; p.wk = (const char*)w_krsc; p.x = (const char*)x;
+    p.dx = (char*)dx; p.part = (float*)workspace;
+    p.M = (int)M; p.m_per_split = (int)mps; p.nsplit = nsplit;
+    p.g_bytes = (unsigned int)gyb; p.x_bytes = (unsigned int)xb;
+    cn_set_last_kernel("jbwd_kernel_ry<%s, 256, 64, 128>", dtype == CN_F16 ? "f16_t" : "bf16_t");
+    if (dtype == CN_F16) CN_LAUNCH((jbwd_kernel_ry<f16_t, 256, 64, 128>), dim3((unsigned)nsplit), dim3(512), st, p);
+    else CN_LAUNCH((jbwd_kernel_ry<bf16_t, 256, 64, 128>), dim3((unsigned)nsplit), dim3(512), st, p);
+    int rc = cn_check_launch("jbwd_ry");
+    if (rc) return rc;
   }
   if (phase == 1) return CN_OK;
   return wg_launch_reduce(st, (const float*)workspace, dw_krsc, nsplit, K, 1, C, C, beta, scale);
+}
+extern "C" cn_status cn_conv2d_bwd1x1_lazy(const void* x, const void* g, const void* bn_y, const float* coef,
+                                           const void* w_crsk, void* dx, float* dw_krsc, int N, int H, int W, int C, int K,
+                                           int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
+                                           void* stream) {
+  if (bn_y == nullptr) { cn_set_error("conv2d_bwd1x1_lazy: null operand"); return CN_EINVAL; }
+  return jb_run(x, g, bn_y, coef, w_crsk, nullptr, dx, dw_krsc, N, H, W, C, K, dtype, beta, scale, workspace, ws_bytes, stream);
+}
+// The same for bn_y = conv1x1(x, w), no bias: bn_y is not read but recomputed from x and w_krsc (the filter's [K][C]
+// copy) with cn_conv2d_fwd's instructions, so dx and dw have the bits cn_conv2d_bwd1x1_lazy gives for the stored y.
+extern "C" cn_status cn_conv2d_bwd1x1_lazy_ry(const void* x, const void* g, const float* coef, const void* w_crsk,
+                                              const void* w_krsc, void* dx, float* dw_krsc, int N, int H, int W, int C,
+                                              int K, int dtype, float beta, float scale, void* workspace, size_t ws_bytes,
+                                              void* stream) {
+  if (w_krsc == nullptr) { cn_set_error("conv2d_bwd1x1_lazy: null operand"); return CN_EINVAL; }
+  return jb_run(x, g, nullptr, coef, w_crsk, w_krsc, dx, dw_krsc, N, H, W, C, K, dtype, beta, scale, workspace, ws_bytes, stream);
 }

@@ -36,6 +36,7 @@ _DEFAULTS = {
     'lazy_z': 1,               # junction apply left to the next block's conv1
     'lazy_a': '1',             # inner BatchNorm apply left to its streaming / halo consumer ('1x1': 1x1 consumers only)
     'jpair': 1,                # dgrad + wgrad of a lazy-dy 64 -> 256 convolution in one pass (fp32 summation order differs)
+    'jpair_recompute': 1,      # ... which recomputes the BatchNorm input from x and w where that is this convolution's output
     'jdgrad': 1,               # junction data gradient as a persistent streaming kernel
     'centered_stats': '1',     # statistics centred on the running mean: 0 never, 1 fp32 models, all every dtype
     # ---- kernel families (0 = the tiled implicit-GEMM kernel serves the layer)

@@ -322,6 +322,24 @@ LAZY_Z_SCOPE = [0]
 # chain (cn_conv2d_bwd1x1_lazy): g and y are read once instead of twice.  dx bit-identical, dW differs by fp32
 # summation order.
 JPAIR = flags.on('jpair')
+# ... and where the lazy dy's y is this convolution's own output (y = conv1x1(x, w), no bias: every site of the model), the
+# kernel does not read y but recomputes it per tile from x and w with the forward kernel's instructions
+# (cn_conv2d_bwd1x1_lazy_ry): one junction-sized read less, dx and dW bit-identical.  The call site says so by running
+# conv2d_bwd1x1_lazy inside `bn_y_is_output_of(w_krsc)`; callers with an arbitrary bn_y keep the kernel that reads it.
+JPAIR_RECOMPUTE = flags.on('jpair_recompute')
+_BN_Y_PRODUCER = [None]
+
+
+@contextlib.contextmanager
+def bn_y_is_output_of(w_krsc):
+    """Inside: the bn_y handed to conv2d_bwd1x1_lazy is conv1x1(x, w) of ITS x, with w_krsc the filter's [K][C] copy."""
+    prev, _BN_Y_PRODUCER[0] = _BN_Y_PRODUCER[0], w_krsc
+    try:
+        yield
+    finally:
+        _BN_Y_PRODUCER[0] = prev
+
+
 # Streaming junction kernel (round 3): the fused junction data gradient (conv1's dgrad + shortcut gradient + ReLU mask +
 # BatchNorm-backward sums) of the instantiated large shapes runs as one persistent streaming kernel
 # (cn_conv2d_dgrad_junction, csrc/junction.hip) instead of the tiled GEMM kernel's epilogue.  g bit-identical, the
@@ -714,11 +732,17 @@ def conv2d_bwd1x1_lazy(x, g, bn_y, coef, w_crsk, dw_krsc, K, beta=1.0, scale=1.0
     need = L.cn_conv2d_bwd1x1_lazy_workspace(N, H, W, C, K)
     ws = workspace(need, x.device, 'main')
     dx = torch.empty_like(x)
+    w_krsc = _BN_Y_PRODUCER[0]      # bn_y = conv1x1(x, w): recomputed, not read (its FLOPs are not algorithmic work)
 
     def call():
-        L.cn_conv2d_bwd1x1_lazy(ptr(x), ptr(g), ptr(bn_y), ptr(coef), ptr(w_crsk), ptr(dx), ptr(dw_krsc), N, H, W, C,
-                                K, code, beta, scale, ptr(ws), ws.numel() * 4, stream_of(x))
-    _wgrad_two_phase(call, x.device, 4.0 * g.numel() * C, 2 * g.numel() * _esize(g) + 2 * x.numel() * _esize(x) + float(need),
+        if w_krsc is not None:
+            L.cn_conv2d_bwd1x1_lazy_ry(ptr(x), ptr(g), ptr(coef), ptr(w_crsk), ptr(w_krsc), ptr(dx), ptr(dw_krsc), N, H,
+                                       W, C, K, code, beta, scale, ptr(ws), ws.numel() * 4, stream_of(x))
+        else:
+            L.cn_conv2d_bwd1x1_lazy(ptr(x), ptr(g), ptr(bn_y), ptr(coef), ptr(w_crsk), ptr(dx), ptr(dw_krsc), N, H, W, C,
+                                    K, code, beta, scale, ptr(ws), ws.numel() * 4, stream_of(x))
+    _wgrad_two_phase(call, x.device, 4.0 * g.numel() * C,
+                     (1 if w_krsc is not None else 2) * g.numel() * _esize(g) + 2 * x.numel() * _esize(x) + float(need),
                      float(need) + K * C * 4, _conv_detail('dgrad+wgrad', C, H, K, 1, (1, 1)), suffix=' [lazy dy]')
     return dx
 
@@ -1126,7 +1150,10 @@ class Conv2dFunction(Function):
                 # junction pair: both gradients of this convolution in one pass over (g, bn_y), on the backward chain
                 if holder is not None and holder.dres is not None:
                     raise _lib.ConvNetHipError('lazy dy met a fused-addend dgrad: the junction layout changed')
-                dx = conv2d_bwd1x1_lazy(x, g, bn_y, coef, mod.w_crsk, mod.grad_view('weight'), mod.out_channels)
+                # (the mailbox entry was matched against this convolution's output: without a bias bn_y IS conv1x1(x, w))
+                own = JPAIR_RECOMPUTE and not ctx.has_bias and _owner_key(bn_y) == ctx.out_key
+                with bn_y_is_output_of(mod.w_krsc if own else None):
+                    dx = conv2d_bwd1x1_lazy(x, g, bn_y, coef, mod.w_crsk, mod.grad_view('weight'), mod.out_channels)
                 mod._notify_grad_ready()
                 COUNTERS['jpair'] = COUNTERS.get('jpair', 0) + 1
                 if holder is not None:

@@ -281,6 +281,12 @@ size_t cn_conv2d_bwd1x1_lazy_workspace(int N, int H, int W, int C, int K);
 cn_status cn_conv2d_bwd1x1_lazy(const void* x, const void* g, const void* bn_y, const float* coef, const void* w_crsk, void* dx,
                                 float* dw_krsc, int N, int H, int W, int C, int K, int dtype, float beta, float scale,
                                 void* workspace, size_t ws_bytes, void* stream);
+/* The same where bn_y is the output of this very convolution (bn_y = conv1x1(x, w), no bias): bn_y is not read but
+ * recomputed per tile from x and w_krsc (the filter as [K][C]) with cn_conv2d_fwd's instructions and rounding.  Same
+ * shapes, workspace and split planning; dx and dw_krsc have the bits cn_conv2d_bwd1x1_lazy gives for the stored output. */
+cn_status cn_conv2d_bwd1x1_lazy_ry(const void* x, const void* g, const float* coef, const void* w_crsk, const void* w_krsc,
+                                   void* dx, float* dw_krsc, int N, int H, int W, int C, int K, int dtype, float beta,
+                                   float scale, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- nn.BatchNorm2d (+ fused residual add + ReLU) (models/resnet.py:128-134,141-165) -------- */
 size_t cn_bn_workspace(int M, int C, int dtype);
